@@ -12,9 +12,14 @@ owns one 2^30-element strip (weak scaling: per-GPU work fixed); the axis-0 sum
 combines the per-rank partials with an RCCL reduce-scatter, the axis-1 sum is
 local.  ``--strong`` keeps the global array at 2^30 instead.
 
-Also reported (secondary, ``dot``): ``dot(A, B)`` for 32768^2 fp32 (configs[3])
-in GFLOP/s, and the CPU baseline (the reference's multi-worker NumPy model,
-oracle/cpu_baseline.py) on a bounded sample.
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line; ``--dump-outputs DIR`` also writes the last timed step's two results.
+``--full`` adds everything else: the cold-start probe, the post-timing checks
+against fp64 restatements, the axis=None / materialised-map extras, the vendor
+reduction, ``dot(A, B)`` for 32768^2 fp32 / fp64 (configs[3]) in GFLOP/s, the
+lreg and k-means legs, and the CPU baseline (the reference's multi-worker NumPy
+model, oracle/cpu_baseline.py) on a bounded sample; ``--dot``, ``--workloads``
+and ``--cpu-baseline`` choose among those legs.
 """
 import argparse
 import json
@@ -76,16 +81,24 @@ def main():
   ap.add_argument('--steps', type=int, default=10)
   ap.add_argument('--warmup', type=int, default=2)
   ap.add_argument('--size', type=int, default=32768)
-  ap.add_argument('--dot', type=int, default=1, help='also time the dot config (1/0)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run the cold-start probe, the post-timing checks, the cfg2 extras, the vendor '
+                       'comparisons, the dot / lreg / k-means legs and the CPU baseline (off: the headline only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the results of the last timed step to DIR/axis0.npy and DIR/axis1.npy (float32)')
+  ap.add_argument('--dot', type=int, default=1, help='--full: also time the dot config (1/0)')
   ap.add_argument('--dot-size', type=int, default=32768)
-  ap.add_argument('--cpu-baseline', type=int, default=1)
+  ap.add_argument('--cpu-baseline', type=int, default=1, help='--full: also run the CPU baseline (1/0)')
   ap.add_argument('--cpu-rows', type=int, default=32768, help='rows of the CPU baseline sample (full cfg2 strip: ~10-20 s of CPU work)')
   ap.add_argument('--strong', action='store_true', help='fixed 2^30 global array (strong scaling)')
   ap.add_argument('--workloads', default='1',
-                  help='also time k-means (cfg3) and lreg (cfg5): 1 / 0, or a comma list of lreg, kmeans, kmeans_api')
+                  help='--full: also time k-means (cfg3) and lreg (cfg5): 1 / 0, or a comma list of lreg, kmeans, '
+                       'kmeans_api')
   ap.add_argument('--km-points', type=int, default=100000000)
   ap.add_argument('--lreg-points', type=int, default=100000000)
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be at least 1 and --warmup at least 0')
 
   import torch
   import spartan_amd
@@ -118,7 +131,7 @@ def main():
     a1 = expr.sum(X * Y + expr.exp(Z), axis=1).optimized().force()
     return a0, a1
 
-  cold = cold_start(expr, X, Y, Z, sync)
+  cold = cold_start(expr, X, Y, Z, sync) if args.full else None
   for _ in range(args.warmup):
     step()
   sync()
@@ -189,6 +202,13 @@ def main():
                    'axis0_ms': round(float(np.mean(ax0)) * 1e3, 4) if ax0 else None,
                    'axis1_ms': round(float(np.mean(ax1)) * 1e3, 4) if ax1 else None},
   }
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, last, ctx)
+  if not args.full:
+    if ctx.rank == 0:
+      print(json.dumps(result), flush=True)
+    spartan_amd.shutdown()
+    return
   result['checked'] = check_cfg2(last, x, y, z, R, S)
   result['cold_start'] = cold
   # SURVEY 8(d) cfg2 also: axis=None, and the materialised map (16 B/elem)
@@ -266,6 +286,18 @@ def main():
   if failed:
     sys.stderr.write('bench.py: post-timing validation FAILED for %s\n' % ', '.join(failed))
     sys.exit(3)
+
+
+def dump_outputs(dirname, last, ctx):
+  """What the timed path returned in its last step: the axis-0 sums (one per
+  column) and the axis-1 sums (one per row of the global array), as float32
+  .npy files.  Every rank takes part in the gather; rank 0 writes."""
+  from spartan_amd.array import distarray
+  arrays = {'axis0': distarray.glom(last[0]), 'axis1': distarray.glom(last[1])}
+  if ctx.rank == 0:
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+      np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ------------------------------------------------------------------ checks

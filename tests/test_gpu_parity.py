@@ -1257,7 +1257,7 @@ def test_multirank_rehearsal_gpu(tmp_path):
 
 
 def test_bench_two_ranks_gpu():
-  """bench.py --gpus 2 exactly as the driver's scaling sweep starts it by
+  """bench.py --gpus 2 --full as the driver's scaling sweep starts it by
   hand: no RANK in the environment, so bench.py launches its own two ranks
   (launch_ranks -> torch.distributed.run) and relays rank 0's line.  Both
   ranks share this box's one GPU, so the data plane is the gloo rehearsal
@@ -1268,7 +1268,7 @@ def test_bench_two_ranks_gpu():
   import subprocess
   env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
   env.update(SPARTAN_DIST_BACKEND='gloo', SPARTAN_SPMD_GUARD='strict')
-  cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2', '--size', '4096',
+  cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2', '--full', '--size', '4096',
          '--steps', '2', '--warmup', '1', '--dot-size', '2048', '--km-points', '200000', '--lreg-points',
          '200000', '--cpu-baseline', '0']
   r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
@@ -1286,6 +1286,45 @@ def test_bench_two_ranks_gpu():
     assert d[leg].get('checked') is True, (leg, d[leg])
   for dt in ('f32', 'f64'):
     assert d['dot'][dt]['checked'] is True, d['dot']
+
+
+def test_bench_plain_run_dumps_outputs_gpu(tmp_path):
+  """A plain bench.py run (no --full) times exactly --steps steps, prints the
+  headline line without any of the --full legs, and --dump-outputs writes the
+  last step's axis-0 / axis-1 sums as float32 .npy: the same from run to run,
+  and within 1e-5 (the fp32 bound) of fp64 sums of the same fp32 inputs."""
+  import json
+  import subprocess
+  env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+  S = 512
+  got = []
+  for name in ('a', 'b'):
+    out = str(tmp_path / name)
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '1', '--size', str(S),
+           '--steps', '3', '--warmup', '1', '--dump-outputs', out]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+    assert d['unit'] == 'GB/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    # value = algorithmic bytes of the 3 timed steps / their wall time (the line
+    # rounds ms_per_step to 1e-4 ms: under 1e-2 relative for any step over 5 us)
+    total = 2 * (3 * 4 * S * S + 4 * S) * 3
+    assert d['value'] == pytest.approx(total / (d['ms_per_step'] * 3 * 1e-3) / 1e9, rel=1e-2, abs=0.02)
+    for leg in ('checked', 'cold_start', 'cfg2_axis_none', 'cfg2_map', 'vendor_reduce', 'dot', 'lreg', 'kmeans',
+                'kmeans_api', 'cpu_baseline'):
+      assert leg not in d, leg
+    assert sorted(os.listdir(out)) == ['axis0.npy', 'axis1.npy']
+    got.append([np.load(os.path.join(out, f)) for f in ('axis0.npy', 'axis1.npy')])
+  x, y = (rng.rand((S, S), s, np.float32).astype(np.float64) for s in (11, 12))
+  z = rng.rand((S, S), 13, np.float32, -1.0, 1.0).astype(np.float64)
+  m = x * y + np.exp(z)
+  for axis in (0, 1):
+    assert got[0][axis].dtype == np.float32 and got[0][axis].shape == (S,)
+    np.testing.assert_array_equal(got[0][axis], got[1][axis])
+    np.testing.assert_allclose(got[0][axis], m.sum(axis), rtol=1e-5)
 
 
 @pytest.mark.parametrize('W', [1, 3])

@@ -7,7 +7,7 @@ def main():
   d = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith('{')][-1])
   r = d['roofline']
   print('cfg2 %.1f GB/s  %.4f ms/step  kernel %.4f ms  frac %.4f  checked %s' % (
-      d['value'], d['ms_per_step'], r['avg_launch_ms'], r['frac'], d['checked']))
+      d['value'], d['ms_per_step'], r['avg_launch_ms'], r['frac'], d.get('checked', 'not run (no --full)')))
   if 'cold_start' in d:
     print('cold', {k: v for k, v in d['cold_start'].items() if k != 'note'})
   for k in ('cfg2_axis_none', 'cfg2_map'):

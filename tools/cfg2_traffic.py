@@ -33,8 +33,8 @@ def main():
   algo = 3 * 4 * 2 ** 30 + 4 * 32768
   f = sum(fetch) / len(fetch)
   w = sum(write) / len(write)
-  json.dump({'command': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --dot 0 '
-                        '--workloads 0 --cpu-baseline 0 --steps 3 --warmup 1',
+  json.dump({'command': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full '
+                        '--dot 0 --workloads 0 --cpu-baseline 0 --steps 3 --warmup 1',
              'correction': 'KB; FETCH_SIZE x2 on gfx950', 'launches': len(fetch),
              'fetch_bytes_per_launch': f, 'write_bytes_per_launch': w, 'algorithmic_bytes_per_launch': algo,
              'traffic_bytes_per_launch': f + w, 'traffic_over_algorithmic': (f + w) / algo,

@@ -42,7 +42,7 @@ for s in $STEPS; do
       cd $R && step lregtests 600 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread \
         -p no:cacheprovider -k "sgd or lreg or golden or dot_reduce" > $O/lregtests.log 2>&1 ;;
     lregbench)
-      cd $R && step lregbench 600 python3 bench.py --dot 0 --workloads lreg --cpu-baseline 0 > $O/lregbench.json 2> $O/lregbench.err ;;
+      cd $R && step lregbench 600 python3 bench.py --full --dot 0 --workloads lreg --cpu-baseline 0 > $O/lregbench.json 2> $O/lregbench.err ;;
     kmquick)
       # small fused-step cases first (ragged units, same-label units, all K / D shapes)
       cd $R && step kmquick 240 python -u -m pytest tests/test_gpu_parity.py -v --timeout 60 --timeout-method thread \
@@ -72,16 +72,16 @@ for s in $STEPS; do
     kmfit)
       cd $R && step kmfit 240 python3 tools/km_fit_timing.py 100000000 2 $KMFIT_OLD > $O/kmfit.txt 2>&1 ;;
     dotbench)
-      cd $R && step dotbench 600 python3 bench.py --workloads 0 --cpu-baseline 0 --steps 2 --warmup 1 > $O/dotbench.json 2> $O/dotbench.err ;;
+      cd $R && step dotbench 600 python3 bench.py --full --workloads 0 --cpu-baseline 0 --steps 2 --warmup 1 > $O/dotbench.json 2> $O/dotbench.err ;;
     kmtests)
       cd $R && step kmtests 600 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread \
         -p no:cacheprovider -k "kmeans" > $O/kmtests.log 2>&1 ;;
     kmbench)
-      cd $R && step kmbench 600 python3 bench.py --dot 0 --workloads kmeans --cpu-baseline 0 --steps 2 --warmup 1 \
+      cd $R && step kmbench 600 python3 bench.py --full --dot 0 --workloads kmeans --cpu-baseline 0 --steps 2 --warmup 1 \
         > $O/kmbench.json 2> $O/kmbench.err ;;
     kmtrace)
       cd /tmp && step kmtrace 300 rocprofv3 --kernel-trace --stats -d $O/kmtrace -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads kmeans --cpu-baseline 0 --steps 2 --warmup 1 > $O/kmtrace.log 2>&1 ;;
+        -- python3 $R/bench.py --full --dot 0 --workloads kmeans --cpu-baseline 0 --steps 2 --warmup 1 > $O/kmtrace.log 2>&1 ;;
     kstrace)
       # kernel trace of the fused step alone (tools/km_step_once.py at cfg3, second-iteration centres)
       cd /tmp && step kstrace 300 rocprofv3 --kernel-trace --stats -d $O/kstrace -o p --output-format csv \
@@ -148,31 +148,31 @@ for s in $STEPS; do
     gemmseg)
       cd $R && step gemmseg 600 ./tools/bin/gemm_tune 32768 2 seg > $O/gemmseg.txt 2>&1 ;;
     bench)
-      cd $R && step bench 600 python3 bench.py > $O/bench.json 2> $O/bench.err ;;
+      cd $R && step bench 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err ;;
     trace2)
       cd /tmp && step trace2 300 rocprofv3 --kernel-trace --stats -d $O/trace2 -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads 0 --cpu-baseline 0 --steps 20 --warmup 5 > $O/trace2.log 2>&1 ;;
+        -- python3 $R/bench.py --full --dot 0 --workloads 0 --cpu-baseline 0 --steps 20 --warmup 5 > $O/trace2.log 2>&1 ;;
     benchtrace)
       # the default bench (minus the CPU legs) under a kernel trace: its JSON
       # line and the trace come from the SAME run (profiles/ roofline check)
       cd /tmp && step benchtrace 600 rocprofv3 --kernel-trace --stats -d $O/benchtrace -o p --output-format csv \
-        -- python3 $R/bench.py --cpu-baseline 0 > $O/benchtrace.json 2> $O/benchtrace.err ;;
+        -- python3 $R/bench.py --full --cpu-baseline 0 > $O/benchtrace.json 2> $O/benchtrace.err ;;
     traceall)
       cd /tmp && step traceall 600 rocprofv3 --kernel-trace --stats -d $O/traceall -o p --output-format csv \
-        -- python3 $R/bench.py --cpu-baseline 0 --steps 5 --warmup 1 > $O/traceall.log 2>&1 ;;
+        -- python3 $R/bench.py --full --cpu-baseline 0 --steps 5 --warmup 1 > $O/traceall.log 2>&1 ;;
     trace5)
       cd /tmp && step trace5 300 rocprofv3 --kernel-trace --stats -d $O/trace5 -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/trace5.log 2>&1 ;;
+        -- python3 $R/bench.py --full --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/trace5.log 2>&1 ;;
     lregpmc)
       cd /tmp && step lregf 300 rocprofv3 --pmc FETCH_SIZE -d $O/lregf -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/lregf.log 2>&1
+        -- python3 $R/bench.py --full --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/lregf.log 2>&1
       cd /tmp && step lregw 300 rocprofv3 --pmc WRITE_SIZE -d $O/lregw -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/lregw.log 2>&1 ;;
+        -- python3 $R/bench.py --full --dot 0 --workloads lreg --cpu-baseline 0 --steps 2 --warmup 1 > $O/lregw.log 2>&1 ;;
     cfg2pmc)
       cd /tmp && step c2f 300 rocprofv3 --pmc FETCH_SIZE -d $O/c2f -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads 0 --cpu-baseline 0 --steps 3 --warmup 1 > $O/c2f.log 2>&1
+        -- python3 $R/bench.py --full --dot 0 --workloads 0 --cpu-baseline 0 --steps 3 --warmup 1 > $O/c2f.log 2>&1
       cd /tmp && step c2w 300 rocprofv3 --pmc WRITE_SIZE -d $O/c2w -o p --output-format csv \
-        -- python3 $R/bench.py --dot 0 --workloads 0 --cpu-baseline 0 --steps 3 --warmup 1 > $O/c2w.log 2>&1 ;;
+        -- python3 $R/bench.py --full --dot 0 --workloads 0 --cpu-baseline 0 --steps 3 --warmup 1 > $O/c2w.log 2>&1 ;;
     kmpmc)
       cd /tmp && step kmf 300 rocprofv3 --pmc FETCH_SIZE -d $O/kmf -o p --output-format csv \
         -- python3 $R/tools/km_step_once.py 100000000 2 > $O/kmf.log 2>&1

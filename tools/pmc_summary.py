@@ -34,7 +34,7 @@ def main():
   fetch = [2.0 * v for k in red for v in f2[k]]
   write = [v for k in red for v in w2.get(k, [])]
   algo = 3 * 4 * 2 ** 30 + 4 * 32768
-  c2 = {'command': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --dot 0 '
+  c2 = {'command': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --dot 0 '
                    '--workloads 0 --cpu-baseline 0 --steps 3 --warmup 1',
         'correction': 'KB; FETCH_SIZE x2 on gfx950', 'launches': len(fetch),
         'fetch_bytes_per_launch': sum(fetch) / max(len(fetch), 1),
