@@ -29,6 +29,7 @@ extern "C" {
 #endif
 
 #define SPX_ABI_VERSION 3  /* 2: spx_kmeans_assign dist_dtype; collectives; 3: spx_kmeans_step */
+/* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan */
 
 /* error codes */
 #define SPX_OK 0
@@ -235,6 +236,33 @@ int spx_cdist(int dtype, int out_dtype, int64_t N, int64_t D, int64_t K, const v
  * skipped; overwritten when zero_first != 0): np.bincount(labels,
  * minlength=K) of kmeans_count_mapper (k_means_.py:61-64).  Exact. */
 int spx_bincount(const int64_t* labels, int64_t N, int64_t K, uint64_t* counts, int zero_first, void* stream);
+
+/* ------------------------------------------------------------ prefix scan
+ * np.cumsum along one axis of a tile: the per-tile scan_fn of _scan_mapper and
+ * the per-tile reduce_fn of _scan_reduce_mapper (spartan/expr/scan.py:24-64).
+ * `in` is a dense row-major block viewed as (outer, n, inner); the scan runs
+ * along n for each of the outer * inner lines.  Additive since ABI 3.
+ * Result dtype as np.cumsum: BOOL / I32 / I64 in -> I64 out, F32 -> F32,
+ * F64 -> F64.  The accumulator is 64-bit integer (unsigned arithmetic, so
+ * wrap-around is defined) for the integer inputs and fp64 for both float
+ * types: an fp32 scan is accumulated in fp64 and rounded once on store.
+ * carry / totals are dense (outer, inner) arrays in the accumulator dtype
+ * (I64 / F64), so bases are never rounded between tiles or ranks.
+ *   carry   NULL, or added to every element of its line;
+ *   totals  NULL, or receives each line's inclusive total WITHOUT the carry;
+ *   out     NULL for a totals-only pass (out and totals both NULL: SPX_EINVAL);
+ *   exclusive != 0: out[i] = carry + sum of in[j], j < i.
+ * Lines that are long and too few to fill the GPU are cut into chunks over
+ * three launches (chunk totals, their scan, the chunk scans): the input is
+ * then read twice, and workspace_bytes must be at least
+ * spx_scan_workspace(in_dtype, outer, n, inner) (0 for the single-pass
+ * geometry; < 0 on bad arguments).  No launch has one workgroup wait for
+ * another.  Fixed addition order, no atomics: the same input and geometry
+ * give the same bits.  Arguments are checked before any device work. */
+int64_t spx_scan_workspace(int in_dtype, int64_t outer, int64_t n, int64_t inner);
+int spx_scan(int in_dtype, const void* in, void* out, int64_t outer, int64_t n, int64_t inner,
+             const void* carry, void* totals, int exclusive, void* workspace, size_t workspace_bytes,
+             void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

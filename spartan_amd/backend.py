@@ -105,6 +105,10 @@ _SIGS = {
                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     'spx_bincount': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                       ctypes.c_void_p], ctypes.c_int),
+    'spx_scan_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
+    'spx_scan': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                  ctypes.c_void_p], ctypes.c_int),
     'spx_comm_load': ([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -169,6 +173,31 @@ def mincost_tiling(t, edges, split_pairs):
   if rc != 0:
     raise ValueError('spx_mincost_tiling: malformed tiling graph')
   return [u for u in range(int(t)) if chosen[u]], int(total.value)
+
+
+SCAN_CHUNK = 32768  # elements of a line per chunk of a chunked scan (csrc/scan_kernels.h)
+
+
+def scan_dtypes(dt):
+  """(result dtype, accumulator dtype) of a cumulative sum over ``dt``:
+  np.cumsum's result dtype; carries and totals are int64 / float64."""
+  dt = np.dtype(dt)
+  spx_dtype(dt)
+  if dt.kind == 'f':
+    return dt, np.dtype(np.float64)
+  return np.dtype(np.int64), np.dtype(np.int64)
+
+
+def scan_plan(outer, n, inner, dtype):
+  """(mode, chunk) spx_scan uses for an (outer, n, inner) scan of ``dtype``:
+  'line' (one pass, a workgroup or wave walks whole lines; chunk == n) or
+  'chunked' (lines cut into SCAN_CHUNK elements over three launches).  The
+  library decides from the geometry and the CU count; a chunked scan is the
+  one that needs a workspace."""
+  need = load_library().spx_scan_workspace(spx_dtype(dtype), int(outer), int(n), int(inner))
+  if need < 0:
+    raise ValueError('scan_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
+  return ('chunked', SCAN_CHUNK) if need > 0 else ('line', int(n))
 
 
 def _arr(vals):
@@ -818,6 +847,39 @@ class HipBackend:
     _check(self.lib.spx_bincount(ctypes.c_void_p(labels.data_ptr()), labels.numel(), counts.numel(),
                                  ctypes.c_void_p(counts.data_ptr()), 1 if zero_first else 0, self.stream()),
            'spx_bincount')
+
+  # ----------------------------------------------------------------- scan
+  def scan(self, src, out, axis_geom, carry=None, totals=None, exclusive=False):
+    """Cumulative sum of the contiguous tensor ``src`` viewed as (outer, n,
+    inner) = ``axis_geom`` along n (spx_scan).  ``out`` (np.cumsum's dtype for
+    src's) may be None for a totals-only pass; ``carry`` / ``totals`` are
+    contiguous (outer, inner) tensors in the accumulator dtype (int64 /
+    float64): carry is added to every element of its line, totals receives
+    each line's inclusive total without the carry.  exclusive: out[i] = carry
+    + the sum before i.  Asynchronous on the current stream."""
+    outer, n, inner = (int(v) for v in axis_geom)
+    dt = np_dtype(src.dtype)
+    odt, adt = scan_dtypes(dt)
+    if not src.is_contiguous() or src.numel() != outer * n * inner:
+      raise ValueError('scan: src must be contiguous with %d elements' % (outer * n * inner))
+    if out is not None and (np_dtype(out.dtype) != odt or not out.is_contiguous() or out.numel() != src.numel()):
+      raise ValueError('scan: out must be a contiguous %s tensor of src\'s size' % odt)
+    for name, t in (('carry', carry), ('totals', totals)):
+      if t is not None and (np_dtype(t.dtype) != adt or not t.is_contiguous() or t.numel() != outer * inner):
+        raise ValueError('scan: %s must be a contiguous %s tensor of %d elements' % (name, adt, outer * inner))
+    need = self.lib.spx_scan_workspace(spx_dtype(dt), outer, n, inner)
+    if need < 0:
+      raise ValueError('scan: bad geometry %s' % (axis_geom,))
+    ws = self._workspace(int(need), src.device) if need > 0 else None
+    ev = self._aot_events('spx_scan')
+    _check(self.lib.spx_scan(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()),
+                             ctypes.c_void_p(out.data_ptr() if out is not None else 0), outer, n, inner,
+                             ctypes.c_void_p(carry.data_ptr() if carry is not None else 0),
+                             ctypes.c_void_p(totals.data_ptr() if totals is not None else 0),
+                             1 if exclusive else 0, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
+                             ws.numel() if ws is not None else 0, self.stream()), 'spx_scan')
+    if ev is not None:
+      ev[1].record()
 
   def kmeans_counters(self, D):
     """Diagnostic (tests, tools): the four u32 counters of the last

@@ -4017,6 +4017,9 @@ extern "C" int spx_bincount(const int64_t* labels, int64_t N, int64_t K, uint64_
   return SPX_OK;
 }
 
+// ============================================================ prefix scan
+#include "scan_kernels.h"
+
 // ============================================================ JIT modules
 extern "C" int spx_module_load(const void* image, size_t nbytes, void** module_out) {
   if (!image || nbytes == 0 || !module_out) return set_err(SPX_EINVAL, "spx_module_load: bad args");

@@ -13,6 +13,7 @@ from .map_with_location import map_with_location, region_map
 from .ndarray import ndarray
 from .reduce import reduce
 from .reshape import reshape
+from .scan import scan
 from .slice import slice_expr
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write
