@@ -881,15 +881,29 @@ class HipBackend:
     if ev is not None:
       ev[1].record()
 
+  @staticmethod
+  def _kmeans_counters_offset(D):
+    """Byte offset of KmWs::ctr (the 64-byte KmCounters block) in a
+    spx_kmeans_assign / spx_kmeans_step workspace for K <= 256: it mirrors
+    km_layout_assign in csrc/kmeans_kernels.h -- CT (D x 256 f32) | cn (256
+    f64) | cmax (4 f64) | ctr.  The only Python statement of that layout."""
+    return D * 256 * 4 + 256 * 8 + 32
+
   def kmeans_counters(self, D):
-    """Diagnostic (tests, tools): the four u32 counters of the last
-    spx_kmeans_assign / spx_kmeans_step workspace in the certified screens'
-    layout (K <= 256; spx.hip KmWs): [rows sent to the all-centre exact
-    kernel, candidate rows, rows left undecided by the bf16x3 pass, rows left
-    undecided by the fp16 screen]."""
+    """Diagnostic (tests, tools): KmCounters::n of the last spx_kmeans_assign
+    / spx_kmeans_step workspace (K <= 256): [rows sent to the all-centre
+    exact kernel, candidate rows, rows left undecided by the bf16x3 pass, rows
+    left undecided by the fp16 screen]."""
     import torch
-    off = (D * 256 * 4 + 15) // 16 * 16 + 256 * 8 + 32
+    off = self._kmeans_counters_offset(D)
     return self._ws[off:off + 16].view(torch.int32).cpu().tolist()
+
+  def kmeans_candidates(self, D, N, count):
+    """Diagnostic (tools): the first ``count`` entries of KmWs::cand_list of
+    that workspace as raw bytes, (count, 40) uint8 -- KfCand = {i64 row; u32
+    mask[8]}.  The list follows KmCounters (64 bytes) and the full list (N i64)."""
+    base = self._kmeans_counters_offset(D) + 64 + N * 8
+    return self._ws[base:base + count * 40].cpu().numpy().reshape(-1, 40)
 
   def _workspace(self, nbytes, device):
     """Grow-only scratch buffer on ``device`` (reuse is stream-ordered)."""

@@ -87,3 +87,57 @@ print('ok')
 ''' % ROOT
   r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
   assert r.returncode == 0 and r.stdout.strip().endswith('ok'), r.stderr[-2000:]
+
+
+# (dtype, N, D, K, assign, accumulate, step): the three workspace sizes as the
+# hand-written formulas before the single layout routines returned them
+# (recorded from a build of that commit; CU count 256, the no-device default
+# and the MI355X's)
+KM_WORKSPACE = [
+  ('F32', 0, 64, 8, 67936, 4160, 206500),
+  ('F32', 1, 3, 1, 5300, 32, 7316),
+  ('F32', 31, 64, 256, 69928, 133120, 4466288),
+  ('F32', 4097, 128, 256, 396968, 34080768, 60074624),
+  ('F32', 70001, 128, 100, 4631296, 26419200, 48235216),
+  ('F32', 9000, 130, 300, 342432, 20121600, 71075916),
+  ('F32', 100000000, 128, 256, 6425133728, 67633152, 8190590372),
+  ('F64', 31, 64, 256, 69928, 266240, 4599408),
+  ('F64', 4097, 128, 256, 396968, 67633152, 93627008),
+  ('F32', 4097, 64, 33, 331176, 2213640, 4245384),
+  ('F32', 32, 64, 1, 69992, 520, 88704),
+  ('F32', 33, 128, 32, 135856, 66048, 1285008),
+  ('F32', 8192, 64, 64, 594272, 8519680, 14558568),
+  ('F32', 8193, 64, 65, 594344, 8652800, 14775684),
+  ('F32', 262144, 64, 128, 16910688, 17039360, 46927332),
+  ('F32', 262145, 128, 129, 16976552, 34080768, 74686208),
+  ('F32', 1000003, 64, 257, 8135288, 17105920, 55322520),
+  ('F32', 5, 1, 1, 3500, 16, 5036),
+  ('F32', 12345, 7, 513, 126504, 2790720, 8670548),
+  ('F64', 0, 1, 1, 3172, 16, 4720),
+  ('F64', 70001, 128, 100, 4631296, 26419200, 48235216),
+  ('F64', 9000, 130, 300, 342432, 20121600, 71075916),
+  ('F32', 2000000, 128, 256, 128633728, 67633152, 255736184),
+  ('F32', 8191, 17, 256, 545892, 9437184, 16148576),
+]
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason='libspx.so not built')
+def test_kmeans_workspace_sizes_without_gpu():
+  """The k-means workspace sizes come from a counting run of the layout
+  routines that also carve the workspace; the memory footprint stays where
+  the earlier formulas had it: within 1 KiB (four 256-byte alignment slacks)
+  either way.  Bad arguments still return -1."""
+  import torch  # noqa: F401
+  lib = ctypes.CDLL(LIB)
+  fns = [getattr(lib, 'spx_kmeans_%s_workspace' % n) for n in ('assign', 'accumulate', 'step')]
+  for f in fns:
+    f.restype = ctypes.c_int64
+    f.argtypes = [ctypes.c_int] + [ctypes.c_int64] * 3
+  code = {'F32': 3, 'F64': 4}
+  for dt, N, D, K, *want in KM_WORKSPACE:
+    for f, parent in zip(fns, want):
+      new = f(code[dt], N, D, K)
+      assert parent - 1024 <= new <= parent + 1024, (f.__name__, dt, N, D, K, new, parent)
+  for bad in [(3, 1, 0, 1), (3, 1, 1, 0), (3, -1, 1, 1), (2, 1, 1, 1), (5, 1, 1, 1), (0, 1, 1, 1)]:
+    for f in fns:
+      assert f(*bad) == -1, (f.__name__, bad)

@@ -1096,7 +1096,7 @@ def test_kmeans_bf16x3_filter_bit_exact(ex, D, K, mode):
 @pytest.mark.parametrize('kind', ['offset128', 'means', 'clusters64', 'negative', 'wide'])
 def test_kmeans_centred_filters_bit_exact(ex, kind, ddt, mode):
   """Both bf16x3 filters rank centres by cc - 2 x.c' with c' = c - mean(c)
-  (spx.hip k_kmeans_prep_b3): labels stay bit-identical to argmin(cdist) for
+  (kmeans_kernels.h k_kmeans_prep_b3): labels stay bit-identical to argmin(cdist) for
   data far from the origin (the case centring is for), second-iteration
   centres (cluster means, the tight-gap case), tight clusters and negative
   coordinates, in both filter modes and both distance dtypes."""
@@ -1607,6 +1607,41 @@ def test_kmeans_step_windows(ex):
   assert (N + 31) // 32 // 256 > 2 * 504
 
 
+def test_kmeans_step_workspace_base_16_aligned(ex):
+  """spx_kmeans_step through the raw ABI with a workspace base that is 16-byte
+  but not 256-byte aligned, and exactly spx_kmeans_step_workspace bytes behind
+  it: the size function budgets the padding of every field the layout aligns
+  on its absolute address.  Labels, sums and counts equal the aligned run's
+  bit for bit."""
+  import ctypes
+  import torch
+  from spartan_amd import backend
+  be = backend.get()
+  N, D, K = 4097, 64, 33
+  P = torch.empty((N, D), dtype=torch.float32, device='cuda')
+  be.fill(P, backend.FILL_UNIFORM, 0.0, 1.0, 5, (0, 0), (N, D))
+  Cd = P[:K].to(torch.float64).contiguous()
+  need = int(be.lib.spx_kmeans_step_workspace(backend.SPX_F32, N, D, K))
+  assert need > 0
+  ws = torch.empty((need + 16,), dtype=torch.uint8, device='cuda')
+  assert ws.data_ptr() % 256 == 0
+  got = []
+  for shift in (0, 16):
+    lab = torch.full((N,), -7, dtype=torch.int64, device='cuda')
+    sums = torch.empty((K, D), dtype=torch.float64, device='cuda')
+    cnt = torch.empty((K,), dtype=torch.int64, device='cuda')
+    rc = be.lib.spx_kmeans_step(backend.SPX_F32, N, D, K, ctypes.c_void_p(P.data_ptr()), P.stride(0),
+                                ctypes.c_void_p(Cd.data_ptr()), ctypes.c_void_p(lab.data_ptr()),
+                                ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), 1,
+                                ctypes.c_void_p(ws.data_ptr() + shift), need, backend.SPX_F64, be.stream())
+    assert rc == 0, be.lib.spx_last_error()
+    torch.cuda.synchronize()
+    got.append((lab, sums, cnt))
+  for a, b in zip(*got):
+    assert torch.equal(a, b)
+  assert int(got[0][2].sum()) == N and int(got[0][0].min()) >= 0
+
+
 def _centre_sums64(lab, X, K, chunk=1 << 20):
   """Checker: per-centre fp64 sums of the rows of X by label, as a one-hot
   fp64 GEMM per chunk of rows (torch, test-only).  index_add_ would be the
@@ -1668,7 +1703,7 @@ def test_kmeans_step_long_chains(ex, K):
 def test_kmeans_step_same_row_units(ex, N):
   """Every row of every 64-row unit carries the same label (identical rows):
   the adds' table rounds take three rows of a centre and the other 61 go
-  through the ranked tail loop (spx.hip k_kmeans_fs2 add_end) -- the
+  through the ranked tail loop (kmeans_kernels.h k_kmeans_fs2 add_end) -- the
   data-dependent part of the unit loop -- with ragged tails (N not a
   multiple of 64, fewer units than blocks, a single row).  Labels, counts
   and sums as the two-pass path."""

@@ -1,7 +1,7 @@
 // Dev tool: time variants of the k-means centroid accumulation
-// (k_kmeans_accum in spartan_amd/csrc/spx.hip, included so the product
-// kernel is what is timed) against pure streaming floors of the same
-// (group, column-tile) partition.
+// (k_kmeans_accum in spartan_amd/csrc/kmeans_kernels.h, included through
+// spx.hip so the product kernel is what is timed) against pure streaming
+// floors of the same (group, column-tile) partition.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -o tools/bin/ka_tune tools/ka_tune.hip
 //   ./tools/bin/ka_tune <N> <D> <K>
 #include "../spartan_amd/csrc/spx.hip"

@@ -1,8 +1,8 @@
 // Dev tool: time configurations of the k-means certified filter kernel
-// (k_kmeans_filter in spartan_amd/csrc/spx.hip, included here so the tuner
-// times the product code) on U[0,1) points, interleaved rounds; every
-// configuration must certify the same points with the same labels and leave
-// the same undecided counts as the first.
+// (k_kmeans_filter in spartan_amd/csrc/kmeans_kernels.h, included through
+// spx.hip so the tuner times the product code) on U[0,1) points, interleaved
+// rounds; every configuration must certify the same points with the same
+// labels and leave the same undecided counts as the first.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -o tools/bin/kf_tune tools/kf_tune.hip
 //   ./tools/bin/kf_tune <N> <D> <K> <rounds>
 #include "../spartan_amd/csrc/spx.hip"

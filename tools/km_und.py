@@ -24,15 +24,14 @@ def main():
   lab2 = torch.empty((N,), dtype=torch.int64, device=dev)
   sums = torch.empty((K, D), dtype=torch.float64, device=dev)
   cnt = torch.empty((K,), dtype=torch.int64, device=dev)
-  off = (D * 256 * 4 + 15) // 16 * 16 + 256 * 8 + 32
   cen = pts[:K].to(torch.float64).contiguous()
   for itn in (1, 2, 3):
     be.kmeans_assign(pts, cen, lab)
     torch.cuda.synchronize()
-    ca = be._ws[off:off + 16].view(torch.int32).cpu().tolist()
+    ca = be.kmeans_counters(D)
     be.kmeans_step(pts, cen, lab2, sums, cnt)
     torch.cuda.synchronize()
-    cs = be._ws[off:off + 16].view(torch.int32).cpu().tolist()
+    cs = be.kmeans_counters(D)
     print('iteration %d: assign counters %s (screen undecided %.3f %%) | step counters %s (%.3f %%) | labels equal %s'
           % (itn, ca, 100.0 * ca[3] / N, cs, 100.0 * cs[3] / N, bool(torch.equal(lab, lab2))), flush=True)
     cen = (sums / cnt.clamp(min=1).to(torch.float64).reshape(K, 1)).contiguous()

@@ -23,14 +23,11 @@ lab = torch.empty(n, dtype=torch.int64, device=P.device)
 for it in range(iters):
   be.kmeans_assign(P, c, lab)
   torch.cuda.synchronize()
-  Kp = 256
-  off = (D * Kp * 4 + 15) // 16 * 16 + Kp * 8 + 16
-  cnt = be._ws[off:off + 8].view(torch.int32).cpu().numpy()
+  cnt = be.kmeans_counters(D)
   print('iter %d: full %d (%.4f%%)  candidates %d (%.4f%%)' % (it, cnt[0], 100 * cnt[0] / n, cnt[1], 100 * cnt[1] / n),
         flush=True)
   # candidates per undecided point: KfCand = {i64 row; u32 mask[8]} (40 B)
-  base = off + 16 + n * 8
-  raw = be._ws[base:base + int(cnt[1]) * 40].cpu().numpy().reshape(-1, 40)
+  raw = be.kmeans_candidates(D, n, int(cnt[1]))
   pc = np.unpackbits(raw[:, 8:].copy(), axis=1).sum(1)
   if len(pc):
     print('  candidates per point: mean %.2f  p50 %d  p90 %d  max %d  hist(1..8,>8) %s'

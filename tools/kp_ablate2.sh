@@ -1,6 +1,6 @@
 #!/bin/bash
 # Dev builds (round 5): k_kmeans_pp ablations on the woven matrix role (work
-# removed by text substitution on a copy of spx.hip -- the product source
+# removed by text substitution on a copy of the sources -- the product source
 # carries no switches) -> tools/bin/libspx_NAME.so, built in parallel, timed by
 # tools/gpu_session.sh kab (results wrong by design; only the time is read).
 #   tools/kp_ablate2.sh name...
@@ -9,11 +9,13 @@ set -e
 here=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$here/tools/bin"
 build() {
-  local name=$1 src=$here/tools/bin/spx_$1.hip
-  python3 - "$here/spartan_amd/csrc/spx.hip" "$src" "$name" <<'PY'
+  local name=$1
+  python3 - "$here" "$name" <<'PY'
 import sys
-s = open(sys.argv[1]).read()
-name = sys.argv[3]
+sys.path.insert(0, sys.argv[1] + '/tools')
+from spx_variant import Variant
+name = sys.argv[2]
+v = Variant(name)
 NR = ('const int rnd = av ? (int)((unsigned int)dr >> 16) : 0xffff;', 'const int rnd = 0xffff;')
 M0 = '      if (mf && scr0) acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ca[0][ks], bq[ks % NB], acc0, 0, 0, 0);\n'
 M1 = '      if (mf && scr1) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ca[1][ks], bq[ks % NB], acc1, 0, 0, 0);\n'
@@ -61,18 +63,9 @@ subs = {
   'r_nomatrix': [NR, (MR, MR + '    if (nit >= 0) { load(r, tt + KP_AHEAD); return; }\n')],
 }[name]
 for a, b in subs:
-  assert s.count(a) == 1, (name, a[:60], s.count(a))
-  s = s.replace(a, b)
-root = sys.argv[2].rsplit('/tools/', 1)[0]
-s = s.replace('#include "../../include/spx.h"', '#include "%s/include/spx.h"' % root)
-s = s.replace('#include "gemm_kernels.h"', '#include "%s/spartan_amd/csrc/gemm_kernels.h"' % root)
-open(sys.argv[2], 'w').write(s)
+  v.sub(a, b)
+v.build()
 PY
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 \
-    -mllvm -amdgpu-promote-alloca-to-vector-limit=1024 -o "$here/tools/bin/libspx_$name.so" "$src" \
-    "$here/spartan_amd/csrc/tiling.cpp" "$here/spartan_amd/csrc/comm.cpp" -ldl
-  rm -f "$src"
-  echo "built tools/bin/libspx_$name.so"
 }
 for n in "$@"; do build $n & done
 wait

@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from spartan_amd import backend  # noqa: E402
 
-SEG = ['barrier wait', 'matrix: MFMAs + add round 0', 'matrix: add rounds 1+', 'matrix: stores + loads',
+SEG = ['barrier wait', 'matrix: MFMAs woven with add rounds 0-2 and the stores', 'matrix: setup before the chain',
+       'matrix: later add rounds + loads',
        'vector: part 1 (v3: fold 0 + decide; v5: fold + exv)', 'vector: part 2 (v3: rank + fold 1)',
        'vector: stage',
        'pre-barrier (flush)']

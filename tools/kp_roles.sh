@@ -7,15 +7,13 @@ set -e
 here=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$here/tools/bin"
 name=${1:-kproles}
-src=$here/tools/bin/spx_$name.hip
-python3 - "$here/spartan_amd/csrc/spx.hip" "$src" "$name" <<'PY'
+python3 - "$here" "$name" <<'PY'
 import sys
-s = open(sys.argv[1]).read()
-variant = sys.argv[3]
-def sub(a, b):
-    global s
-    assert s.count(a) == 1, a[:60]
-    s = s.replace(a, b)
+sys.path.insert(0, sys.argv[1] + '/tools')
+from spx_variant import Variant
+variant = sys.argv[2]
+v = Variant(variant)
+sub = v.sub
 sub('template <int KS, int NCT>\nstruct KpStep {', '''__device__ unsigned long long g_kp_roles[1024 * 8 * 4];
 extern "C" int spx_dev_kp_roles(unsigned long long* host_out) {
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_kp_roles), sizeof(g_kp_roles)) == hipSuccess ? 0 : 1;
@@ -59,15 +57,6 @@ extra = {
   'kproles_nostage': [NR, ('      stage(rs, mu4, us);\n', '      p2p[t] = rs[0][0];\n')],
 }[variant]
 for a, b in extra:
-  assert s.count(a) == 1, (variant, a[:60], s.count(a))
-  s = s.replace(a, b)
-root = sys.argv[2].rsplit('/tools/', 1)[0]
-s = s.replace('#include "../../include/spx.h"', '#include "%s/include/spx.h"' % root)
-s = s.replace('#include "gemm_kernels.h"', '#include "%s/spartan_amd/csrc/gemm_kernels.h"' % root)
-open(sys.argv[2], 'w').write(s)
+  sub(a, b)
+v.build()
 PY
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 \
-  -mllvm -amdgpu-promote-alloca-to-vector-limit=1024 -o "$here/tools/bin/libspx_$name.so" "$src" \
-  "$here/spartan_amd/csrc/tiling.cpp" "$here/spartan_amd/csrc/comm.cpp" -ldl
-rm -f "$src"
-echo "built tools/bin/libspx_$name.so"

@@ -1,5 +1,6 @@
 // Dev probe: kb_top2_lanes (k-means filter epilogue step B) against a
-// brute-force top-2 over the 32 lanes of each half.
+// brute-force top-2 over the 32 lanes of each half (kb_top2_lanes lives in
+// spartan_amd/csrc/kmeans_kernels.h, which spx.hip includes).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -o tools/bin/top2_probe tools/top2_probe.hip
 #include "../spartan_amd/csrc/spx.hip"
 #include <algorithm>
