@@ -15,6 +15,7 @@ import os
 import subprocess
 import tempfile
 import threading
+from collections import namedtuple
 
 import numpy as np
 
@@ -43,18 +44,24 @@ def spx_dtype(dt):
   return _DT[dt]
 
 
-def torch_dtype(dt):
+_TORCH_DT, _NP_DT = {}, {}  # NumPy dtype <-> torch dtype, filled on first use (torch is imported lazily)
+
+
+def _dtype_tables():
   import torch
-  return {np.dtype(np.bool_): torch.bool, np.dtype(np.int32): torch.int32,
-          np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32,
-          np.dtype(np.float64): torch.float64}[np.dtype(dt)]
+  pairs = [(np.dtype(name), getattr(torch, name)) for name in ('bool', 'int32', 'int64', 'float32', 'float64')]
+  _NP_DT.update((t, d) for d, t in pairs)
+  _TORCH_DT.update(pairs)
+
+
+def torch_dtype(dt):
+  _TORCH_DT or _dtype_tables()
+  return _TORCH_DT[np.dtype(dt)]
 
 
 def np_dtype(tdt):
-  import torch
-  return {torch.bool: np.dtype(np.bool_), torch.int32: np.dtype(np.int32),
-          torch.int64: np.dtype(np.int64), torch.float32: np.dtype(np.float32),
-          torch.float64: np.dtype(np.float64)}[tdt]
+  _NP_DT or _dtype_tables()
+  return _NP_DT[tdt]
 
 
 # ------------------------------------------------------------------ library
@@ -305,6 +312,123 @@ def _num_cus():
   return _NCU[0]
 
 
+# What backend.reduce launches for one operand layout.  kind .. kint: the
+# kernel (codegen.gen_reduce's arguments); nblk: the grid (0: empty output,
+# nothing to launch); P: partials per output element, n_out of them each, in
+# pdt; direct: the kernel writes the result itself (no finalize pass); args:
+# the KArgs block with dims, strides, aux, flags and the arg-index geometry
+# filled in -- pointers, scalars, out0 / out1 are per call (_run_reduce).
+ReducePlan = namedtuple('ReducePlan', 'kind classes V U rowinv klpr kfull kint nblk P n_out arg direct pdt args')
+
+
+def _lanes(need):
+  """Lanes of a wave per segment / row group: the power of two >= need, at most 64."""
+  lpr = 1
+  while lpr < need and lpr < 64:
+    lpr *= 2
+  return lpr
+
+
+def plan_reduce(root, op, ins, res16, view, out_dtype, idx_geom, ncu):
+  """The ReducePlan of a fused map+reduce: pure integer arithmetic, no device.
+  ins: [(slot, NumPy dtype)] in slot order; res16: per input its pointer's
+  residue mod 16 (vec_width keeps V * itemsize <= 16, so the residue decides
+  the vector path); view: layout.reduce_view's (O, R, I, per-input strides);
+  ncu: the device's CU count.  Reads the module's grid / layout knobs."""
+  O, R, I, vstr = view
+  n_out = O * I
+  arg = op in ('argmin', 'argmax')
+  adt = codegen.acc_dtype(op, root.dtype)
+  if n_out == 0:
+    return ReducePlan(None, (), 1, None, (), None, False, False, 0, 1, 0, arg, True, adt, None)
+  if R == 0:
+    raise ValueError('zero-size reduction')
+  V = codegen.vec_width([dt for _, dt in ins] + [adt])
+  rowdot = bool(codegen.rowdots(root))
+  # the vectorised dim (R of the (O, R) forms, I of (O, R, I)): its extent, every
+  # pointer and a contiguous input's other strides must be multiples of V
+  vd, n = (1, R) if I == 1 else (2, I)
+  classes = tuple(_cls(st[vd]) for st in vstr)
+  vec_ok = V > 1 and n % V == 0 and all(
+      res16[k] % (V * np.dtype(dt).itemsize) == 0 and
+      (classes[k] != 'c' or all(vstr[k][d] % V == 0 for d in range(3) if d != vd))
+      for k, (_, dt) in enumerate(ins))
+  per = V if vec_ok else 1
+  args = codegen.KArgs()
+  for k, (s, _) in enumerate(ins):
+    for d in range(3):
+      args.str[s][d] = vstr[k][d]
+  args.dim[0], args.dim[1], args.dim[2] = O, R, I
+  args.flags = 1 if vec_ok else 0
+  target_blocks = 2048
+  P, lpr, CT = 1, None, None
+  if I == 1 and R <= 64 * V * 16:
+    # short segments: several per wave (LPR lanes each), grid-stride over O
+    kind = 'rowsp'
+    lpr = _lanes(-(-R // per))
+    seg_per_block = 4 * (64 // lpr)
+    nblk = max(1, min(-(-O // seg_per_block), 256 * 16))
+    args.aux[0], args.aux[1], args.aux[2] = 1, R, lpr.bit_length() - 1
+  elif I == 1:
+    kind = 'rows'
+    if O < target_blocks:
+      P = max(1, min(-(-target_blocks // O), -(-R // (256 * per * 4))))
+    chunk = -(-R // P)
+    chunk = -(-chunk // per) * per
+    P = -(-R // chunk)
+    # grid-stride kernel: at most ROWS_GRID_PER_CU resident blocks per CU
+    # stream the segments
+    nblk = min(O * P, ROWS_GRID_PER_CU * ncu)
+    args.aux[0], args.aux[1] = P, chunk
+  else:
+    kind = 'cols'
+    lpr = _lanes(-(-I // per))
+    CT = -(-I // (lpr * per))
+    rows_per_step = 4 * (64 // lpr)
+    base = CT * O
+    # wide column reductions (several column tiles) stream best with
+    # exactly two resident blocks per CU (cfg2 axis 0: 512 blocks 1.80 ms,
+    # 1024 1.87, 2048 1.87, 4096 1.90); one narrow column tile (cfg5's 64
+    # columns) with eight (2048: 4.06 ms per lreg iteration, 512: 4.15)
+    # -- profiles/r02_cfg2_grid.txt; a fused row dot (cfg5's gradient, one
+    # 64-column tile) with ROWDOT_BLOCKS_PER_CU (one, its rows interleaved
+    # over the blocks: see ROWDOT_INTERLEAVE)
+    tb = (COLS_BLOCKS_PER_CU if CT > 1 else ROWDOT_BLOCKS_PER_CU if rowdot else 8) * ncu
+    if base < tb:
+      P = max(1, min(-(-tb // base), -(-R // (rows_per_step * 4))))
+    chunk = -(-R // P)
+    P = -(-R // chunk)
+    nblk = base * P
+    args.aux[0], args.aux[1], args.aux[2], args.aux[3] = P, chunk, lpr.bit_length() - 1, CT
+  if rowdot and (kind != 'cols' or CT != 1):
+    raise NotImplementedError('fused row dot needs each row in one lane group (K <= 64 * vector width)')
+  if nblk > 0x7fffffff:
+    raise NotImplementedError('reduction grid too large')
+  if arg:
+    g = idx_geom or {}
+    args.aux[4] = g.get('offset', 0)
+    args.aux[5] = 1 if g.get('decompose') else 0
+    if g.get('decompose'):
+      tshape, tul, ashape = g['tshape'], g['tul'], g['ashape']
+      args.aux[6] = len(tshape)
+      for d in range(len(tshape)):
+        args.tshape[d], args.tul[d], args.ashape[d] = tshape[d], tul[d], ashape[d]
+  U, rowinv, klpr, kfull = None, (), None, False
+  if kind == 'cols':
+    U = ROWDOT_UNROLL if rowdot else codegen.cols_unroll(ins, classes, V, [st[1] for st in vstr])
+    rowinv = tuple(s for (s, _), st in zip(ins, vstr) if st[1] == 0)
+    # a fused row dot's lane group width (and whether the vector path covers
+    # the columns exactly) is compiled in: its per-row lane sum is then
+    # straight-line DPP (codegen.gen_reduce)
+    if rowdot:
+      klpr, kfull = lpr, bool(vec_ok and I == lpr * per)
+  kint = bool((klpr and ROWDOT_INTERLEAVE) or (kind == 'cols' and CT > 1 and op == 'sum' and COLS_INTERLEAVE))
+  # partials' dtype: fp64 for an interleaved fp32 sum (codegen.partial_dtype)
+  pdt = codegen.partial_dtype(op, adt, kint) if kind == 'cols' else adt
+  direct = P == 1 and (arg or pdt == np.dtype(out_dtype))
+  return ReducePlan(kind, classes, V, U, rowinv, klpr, kfull, kint, nblk, P, n_out, arg, direct, pdt, args)
+
+
 class HipBackend:
   """Launches libspx.so / generated kernels on the current HIP stream."""
   name = 'hip'
@@ -344,15 +468,22 @@ class HipBackend:
       self._names[f.value] = name
       return f
 
-  def _aot_events(self, name):
-    """(start, end) HIP events around one ahead-of-time libspx call on the
-    current stream when bench timing is on (kernel_events), else None."""
+  def _events(self):
+    """A (start, end) pair of HIP events, start recorded on the current
+    stream, when bench timing is on (kernel_events), else None."""
     if self.kernel_events is None:
       return None
     import torch
     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     ev[0].record()
-    self.kernel_events.append((name, ev[0], ev[1]))
+    return ev
+
+  def _aot_events(self, name):
+    """_events() around one ahead-of-time libspx call, logged under ``name``;
+    the caller records the end event."""
+    ev = self._events()
+    if ev is not None:
+      self.kernel_events.append((name, ev[0], ev[1]))
     return ev
 
   def kmeans_timing(self, enable):
@@ -374,11 +505,7 @@ class HipBackend:
     if self.launch_log is not None:
       self.launch_log.append(grid)
     args.grid = grid
-    ev = None
-    if self.kernel_events is not None:
-      import torch
-      ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-      ev[0].record()
+    ev = self._events()
     _check(self.lib.spx_launch(fn, grid, 1, 1, 256, 0, ctypes.byref(args), ctypes.sizeof(args),
                                self.stream()), 'spx_launch')
     if ev is not None:
@@ -454,8 +581,8 @@ class HipBackend:
     import torch
     slots = sorted(inputs)
     # launch plan of an identical call (same IR signature, operand layouts and
-    # shapes: an iterative driver's replayed DAG): everything below up to the
-    # kernel arguments is a function of this key
+    # shapes: an iterative driver's replayed DAG): the view, the plan
+    # (plan_reduce) and the kernel are functions of this key
     # (the pointer's residue mod 16, not just 16-byte alignment: the vector
     # width of narrow types needs only 8 or 4 bytes, so two pointers with the
     # same 16-alignment verdict can still differ in what V they allow)
@@ -466,211 +593,80 @@ class HipBackend:
             # the module's grid / layout knobs shape the plan too
             (ROWS_GRID_PER_CU, COLS_BLOCKS_PER_CU, COLS_INTERLEAVE, ROWDOT_BLOCKS_PER_CU, ROWDOT_UNROLL,
              ROWDOT_INTERLEAVE))
-    plan = self._reduce_plans.get(pkey)
-    if plan is not None:
-      return self._replay_reduce(plan, root, inputs, slots, out_shape, out_dtype)
-    ins = [(s, np_dtype(inputs[s].dtype)) for s in slots]
-    strides = [broadcast_strides(tuple(inputs[s].shape), in_shape, inputs[s].stride()) for s in slots]
-    view = reduce_view(in_shape, strides, axis)
-    if view is None and any(not inputs[s].is_contiguous() for s in slots):
-      # a strided view whose dims do not collapse to (O, R, I): make the
-      # views dense (identity-map kernel) and take the plain path
-      inputs = {s: self.contiguous(t) for s, t in inputs.items()}
-      strides = [broadcast_strides(tuple(inputs[s].shape), in_shape) for s in slots]
+    entry = self._reduce_plans.get(pkey)
+    if entry is None:
+      ins = [(s, np_dtype(inputs[s].dtype)) for s in slots]
+      strides = [broadcast_strides(tuple(inputs[s].shape), in_shape, inputs[s].stride()) for s in slots]
       view = reduce_view(in_shape, strides, axis)
-    if view is None:
-      # inputs broadcast along different dims of an N-d iteration space (e.g.
-      # (N, 1, D) - (1, K, D) reduced over the last axis): the rows of the
-      # (O, R, I) form have no single stride.  Materialise the mapped values
-      # with the N-d map kernel, then reduce that dense array -- in slabs of a
-      # kept dim when the whole iteration space exceeds MATERIALISE_LIMIT bytes.
-      if codegen.rowdots(root):
-        raise NotImplementedError('row-dot reduction over a non-coalescible view')
-      dev = out_device(inputs, slots)
-      esize = np.dtype(root.dtype).itemsize
-      total = prod(in_shape) * esize
-      if axis is not None and total > self.MATERIALISE_LIMIT:
-        kept = [d for d in range(len(in_shape)) if d != axis and in_shape[d] > 1]
-        if kept:
-          return self._reduce_slabs(root, op, inputs, tuple(in_shape), axis, tuple(out_shape), out_dtype,
-                                    idx_geom, kept[0], dev)
-      tmp = torch.empty(tuple(in_shape), dtype=torch_dtype(root.dtype), device=dev)
-      self.map(root, inputs, tmp)
-      return self.reduce(codegen.In(0, root.dtype), op, {0: tmp}, in_shape, axis, out_shape, out_dtype, idx_geom)
-    O, R, I, vstr = view
-    dev = out_device(inputs, slots)
-    n_out = O * I
-    arg = op in ('argmin', 'argmax')
-    adt = codegen.acc_dtype(op, root.dtype)
-    if arg:
-      res_v = torch.empty(tuple(out_shape), dtype=torch_dtype(adt), device=dev)
-      result = torch.empty(tuple(out_shape), dtype=torch.int64, device=dev)
-    else:
-      result = torch.empty(tuple(out_shape), dtype=torch_dtype(out_dtype), device=dev)
-    if n_out == 0:
-      return (res_v, result) if arg else result
-    if R == 0:
-      raise ValueError('zero-size reduction')
-    V = codegen.vec_width([dt for _, dt in ins] + [adt])
-    args = codegen.KArgs()
-    _scalars_into(root, args)
-    for k, s in enumerate(slots):
-      args.ptr[s] = inputs[s].data_ptr()
-      for d in range(3):
-        args.str[s][d] = vstr[k][d]
-    args.dim[0], args.dim[1], args.dim[2] = O, R, I
-    target_blocks = 2048
-    if I == 1 and R <= 64 * V * 16:
-      # short segments: several per wave (LPR lanes each), grid-stride over O
-      kind = 'rowsp'
-      classes = [_cls(vstr[k][1]) for k in range(len(slots))]
-      vec_ok = V > 1 and R % V == 0 and all(
-          _aligned_ptr(inputs[s], V) and (vstr[k][0] % V == 0 if classes[k] == 'c' else True)
-          for k, s in enumerate(slots))
-      per = V if vec_ok else 1
-      need = -(-R // per)
-      lpr = 1
-      while lpr < need and lpr < 64:
-        lpr *= 2
-      seg_per_block = 4 * (64 // lpr)
-      P = 1
-      nblk = max(1, min(-(-O // seg_per_block), 256 * 16))
-      args.aux[0], args.aux[1], args.aux[2] = 1, R, lpr.bit_length() - 1
-    elif I == 1:
-      kind = 'rows'
-      classes = [_cls(vstr[k][1]) for k in range(len(slots))]
-      vec_ok = V > 1 and R % V == 0 and all(
-          _aligned_ptr(inputs[s], V) and (vstr[k][0] % V == 0 if classes[k] == 'c' else True)
-          for k, s in enumerate(slots))
-      per = V if vec_ok else 1
-      P = 1
-      if O < target_blocks:
-        P = max(1, min(-(-target_blocks // O), -(-R // (256 * per * 4))))
-      chunk = -(-R // P)
-      chunk = -(-chunk // per) * per
-      P = -(-R // chunk)
-      nblk = O * P
-      # grid-stride kernel: at most ROWS_GRID_PER_CU resident blocks per CU
-      # stream the segments
-      nblk = min(nblk, ROWS_GRID_PER_CU * _num_cus())
-      args.aux[0], args.aux[1] = P, chunk
-    else:
-      kind = 'cols'
-      classes = [_cls(vstr[k][2]) for k in range(len(slots))]
-      vec_ok = V > 1 and I % V == 0 and all(
-          _aligned_ptr(inputs[s], V) and ((vstr[k][0] % V == 0 and vstr[k][1] % V == 0)
-                                          if classes[k] == 'c' else True)
-          for k, s in enumerate(slots))
-      per = V if vec_ok else 1
-      need = -(-I // per)
-      lpr = 1
-      while lpr < need and lpr < 64:
-        lpr *= 2
-      CT = -(-I // (lpr * per))
-      rows_per_step = 4 * (64 // lpr)
-      base = CT * O
-      P = 1
-      # wide column reductions (several column tiles) stream best with
-      # exactly two resident blocks per CU (cfg2 axis 0: 512 blocks 1.80 ms,
-      # 1024 1.87, 2048 1.87, 4096 1.90); one narrow column tile (cfg5's 64
-      # columns) with eight (2048: 4.06 ms per lreg iteration, 512: 4.15)
-      # -- profiles/r02_cfg2_grid.txt; a fused row dot (cfg5's gradient, one
-      # 64-column tile) with ROWDOT_BLOCKS_PER_CU (one, its rows interleaved
-      # over the blocks: see ROWDOT_INTERLEAVE)
-      rowdot = bool(codegen.rowdots(root))
-      tb = (COLS_BLOCKS_PER_CU if CT > 1 else ROWDOT_BLOCKS_PER_CU if rowdot else 8) * _num_cus()
-      if base < tb:
-        P = max(1, min(-(-tb // base), -(-R // (rows_per_step * 4))))
-      chunk = -(-R // P)
-      P = -(-R // chunk)
-      nblk = base * P
-      args.aux[0], args.aux[1], args.aux[2], args.aux[3] = P, chunk, lpr.bit_length() - 1, CT
-    if codegen.rowdots(root) and (kind != 'cols' or CT != 1):
-      raise NotImplementedError('fused row dot needs each row in one lane group (K <= 64 * vector width)')
-    if nblk > 0x7fffffff:
-      raise NotImplementedError('reduction grid too large')
-    args.flags = 1 if vec_ok else 0
-    if arg:
-      g = idx_geom or {}
-      args.aux[4] = g.get('offset', 0)
-      args.aux[5] = 1 if g.get('decompose') else 0
-      if g.get('decompose'):
-        tshape, tul, ashape = g['tshape'], g['tul'], g['ashape']
-        args.aux[6] = len(tshape)
-        for d in range(len(tshape)):
-          args.tshape[d], args.tul[d], args.ashape[d] = tshape[d], tul[d], ashape[d]
-    # a fused row dot's lane group width (and whether the vector path covers
-    # the columns exactly) is compiled in: its per-row lane sum is then
-    # straight-line DPP (codegen.gen_reduce)
-    klpr, kfull = None, False
-    if kind == 'cols' and codegen.rowdots(root):
-      klpr, kfull = lpr, bool(vec_ok and CT == 1 and I == lpr * per)
-    kint = bool((klpr and ROWDOT_INTERLEAVE) or (kind == 'cols' and CT > 1 and op == 'sum' and COLS_INTERLEAVE))
-    # partials' dtype: fp64 for an interleaved fp32 sum (codegen.partial_dtype)
-    pdt = codegen.partial_dtype(op, adt, kint) if kind == 'cols' else adt
-    if arg:
-      direct = P == 1
-      part_v = res_v if direct else torch.empty((P * n_out,), dtype=torch_dtype(adt), device=dev)
-      part_i = result if direct else torch.empty((P * n_out,), dtype=torch.int64, device=dev)
-    else:
-      direct = (P == 1 and pdt == np.dtype(out_dtype))
-      part_v = result if direct else torch.empty((P * n_out,), dtype=torch_dtype(pdt), device=dev)
-      part_i = None
-    args.out0 = part_v.data_ptr()
-    args.out1 = part_i.data_ptr() if arg else 0
-    U, rowinv = None, ()
-    if kind == 'cols':
-      U = codegen.cols_unroll(ins, classes, V, [vstr[k][1] for k in range(len(slots))])
-      if codegen.rowdots(root):
-        U = ROWDOT_UNROLL
-      rowinv = tuple(s for k, s in enumerate(slots) if vstr[k][1] == 0)
-    sig = ('reduce', root.sig(), tuple(ins), tuple(classes), kind, op, V, U, rowinv, klpr, kfull, kint)
-    fn = self._sig_fns.get(sig)
-    if fn is None:
-      src, kname = codegen.named(codegen.gen_reduce(root, ins, classes, kind, op, V, U, rowinv, klpr, kfull,
-                                                    kint), 'spx_reduce', kind)
-      fn = self._sig_fns[sig] = self.kernel(src, kname)
-    self.launch(fn, nblk, args)
-    if not direct:
-      _check(self.lib.spx_reduce_finalize(
-          OP_CODE[op], spx_dtype(pdt), spx_dtype(np.int64 if arg else out_dtype),
-          ctypes.c_void_p(part_v.data_ptr()), ctypes.c_void_p(part_i.data_ptr() if arg else 0), P, n_out,
-          ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(res_v.data_ptr() if arg else 0),
-          self.stream()), 'spx_reduce_finalize')
-    if len(self._reduce_plans) >= 512:
-      self._reduce_plans.clear()
-    self._reduce_plans[pkey] = (fn, nblk, bytes(args), arg, direct, pdt, P, n_out, dev, OP_CODE[op])
-    return (res_v, result) if arg else result
+      if view is None and any(not inputs[s].is_contiguous() for s in slots):
+        # a strided view whose dims do not collapse to (O, R, I): make the
+        # views dense (identity-map kernel) and reduce those (a call of its
+        # own: the plan belongs to the copies' layout, not to this key)
+        return self.reduce(root, op, {s: self.contiguous(t) for s, t in inputs.items()}, in_shape, axis,
+                           out_shape, out_dtype, idx_geom)
+      if view is None:
+        # inputs broadcast along different dims of an N-d iteration space (e.g.
+        # (N, 1, D) - (1, K, D) reduced over the last axis): the rows of the
+        # (O, R, I) form have no single stride.  Materialise the mapped values
+        # with the N-d map kernel, then reduce that dense array -- in slabs of a
+        # kept dim when the whole iteration space exceeds MATERIALISE_LIMIT bytes.
+        if codegen.rowdots(root):
+          raise NotImplementedError('row-dot reduction over a non-coalescible view')
+        dev = out_device(inputs, slots)
+        total = prod(in_shape) * np.dtype(root.dtype).itemsize
+        if axis is not None and total > self.MATERIALISE_LIMIT:
+          kept = [d for d in range(len(in_shape)) if d != axis and in_shape[d] > 1]
+          if kept:
+            return self._reduce_slabs(root, op, inputs, tuple(in_shape), axis, tuple(out_shape), out_dtype,
+                                      idx_geom, kept[0], dev)
+        tmp = torch.empty(tuple(in_shape), dtype=torch_dtype(root.dtype), device=dev)
+        self.map(root, inputs, tmp)
+        return self.reduce(codegen.In(0, root.dtype), op, {0: tmp}, in_shape, axis, out_shape, out_dtype, idx_geom)
+      plan = plan_reduce(root, op, ins, [inputs[s].data_ptr() % 16 for s in slots], view, out_dtype, idx_geom,
+                         _num_cus())
+      fn = None
+      if plan.nblk:
+        sig = ('reduce', root.sig(), tuple(ins), plan.classes, plan.kind, op, plan.V, plan.U, plan.rowinv,
+               plan.klpr, plan.kfull, plan.kint)
+        fn = self._sig_fns.get(sig)
+        if fn is None:
+          src, kname = codegen.named(codegen.gen_reduce(root, ins, *sig[3:]), 'spx_reduce', plan.kind)
+          fn = self._sig_fns[sig] = self.kernel(src, kname)
+      if len(self._reduce_plans) >= 512:
+        self._reduce_plans.clear()
+      entry = self._reduce_plans[pkey] = (plan, fn, out_device(inputs, slots))
+    return self._run_reduce(entry, root, op, inputs, slots, out_shape, out_dtype)
 
-  def _replay_reduce(self, plan, root, inputs, slots, out_shape, out_dtype):
-    """backend.reduce from a recorded launch plan: the same kernel, grid and
-    argument block, with this call's scalars, pointers and output buffers."""
+  def _run_reduce(self, entry, root, op, inputs, slots, out_shape, out_dtype):
+    """Launch a planned reduction (first call and replay alike): the plan's
+    kernel, grid and argument block with this call's scalars, pointers and
+    output buffers, then the finalize pass over the P partials."""
     import torch
-    fn, nblk, blob, arg, direct, adt, P, n_out, dev, opc = plan
-    args = codegen.KArgs.from_buffer_copy(blob)
+    p, fn, dev = entry
+    tpdt = torch_dtype(p.pdt)  # (arg ops: the values' dtype, pdt == the accumulator's)
+    out_shape = tuple(out_shape)
+    if p.arg:
+      res_v = torch.empty(out_shape, dtype=tpdt, device=dev)
+      result = torch.empty(out_shape, dtype=torch.int64, device=dev)
+    else:
+      res_v, result = None, torch.empty(out_shape, dtype=torch_dtype(out_dtype), device=dev)
+    if p.nblk == 0:  # empty output
+      return (res_v, result) if p.arg else result
+    args = codegen.KArgs.from_buffer_copy(p.args)
     _scalars_into(root, args)
     for s in slots:
       args.ptr[s] = inputs[s].data_ptr()
-    if arg:
-      res_v = torch.empty(tuple(out_shape), dtype=torch_dtype(adt), device=dev)
-      result = torch.empty(tuple(out_shape), dtype=torch.int64, device=dev)
-      part_v = res_v if direct else torch.empty((P * n_out,), dtype=torch_dtype(adt), device=dev)
-      part_i = result if direct else torch.empty((P * n_out,), dtype=torch.int64, device=dev)
+    if p.direct:
+      part_v, part_i = (res_v, result) if p.arg else (result, None)
     else:
-      result = torch.empty(tuple(out_shape), dtype=torch_dtype(out_dtype), device=dev)
-      part_v = result if direct else torch.empty((P * n_out,), dtype=torch_dtype(adt), device=dev)
-      part_i = None
+      part_v = torch.empty((p.P * p.n_out,), dtype=tpdt, device=dev)
+      part_i = torch.empty((p.P * p.n_out,), dtype=torch.int64, device=dev) if p.arg else None
     args.out0 = part_v.data_ptr()
-    args.out1 = part_i.data_ptr() if arg else 0
-    self.launch(fn, nblk, args)
-    if not direct:
-      _check(self.lib.spx_reduce_finalize(
-          opc, spx_dtype(adt),
-          spx_dtype(np.int64 if arg else out_dtype),
-          ctypes.c_void_p(part_v.data_ptr()), ctypes.c_void_p(part_i.data_ptr() if arg else 0), P, n_out,
-          ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(res_v.data_ptr() if arg else 0),
-          self.stream()), 'spx_reduce_finalize')
-    return (res_v, result) if arg else result
+    args.out1 = part_i.data_ptr() if p.arg else 0
+    self.launch(fn, p.nblk, args)
+    if not p.direct:
+      self._finalize(op, p.pdt, np.int64 if p.arg else out_dtype, part_v, part_i, p.P, p.n_out, result, res_v)
+    return (res_v, result) if p.arg else result
 
   def contiguous(self, t, dtype=None):
     """Dense copy of a strided view (and/or dtype conversion) by the generated
@@ -693,11 +689,14 @@ class HipBackend:
   def finalize(self, op, parts, P, n, out):
     """out[i] = fold over p < P of parts[p * n + i] in p order (sum / min /
     max; NaN propagates for min / max like np.minimum / np.maximum)."""
-    dt = spx_dtype(np_dtype(parts.dtype))
-    _check(self.lib.spx_reduce_finalize(OP_CODE[op], dt, spx_dtype(np_dtype(out.dtype)),
-                                        ctypes.c_void_p(parts.data_ptr()), ctypes.c_void_p(0), P, n,
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(0), self.stream()),
-           'spx_reduce_finalize')
+    self._finalize(op, np_dtype(parts.dtype), np_dtype(out.dtype), parts, None, P, n, out, None)
+
+  def _finalize(self, op, pdt, odt, parts, parts_i, P, n, out, out_v):
+    """spx_reduce_finalize: ``parts`` (dtype pdt; arg ops: values, with their
+    indices ``parts_i``) -> ``out`` (dtype odt; arg ops: the indices, values
+    to ``out_v``)."""
+    _check(self.lib.spx_reduce_finalize(OP_CODE[op], spx_dtype(pdt), spx_dtype(odt), _ptr(parts), _ptr(parts_i),
+                                        P, n, _ptr(out), _ptr(out_v), self.stream()), 'spx_reduce_finalize')
 
   def argcombine(self, op, vals, idx):
     """vals/idx: [R, n] -> (val[n], idx[n]) best-of-R with first-index ties."""
@@ -931,13 +930,13 @@ def _cls(stride):
   return 'c' if stride == 1 else ('b' if stride == 0 else 'g')
 
 
-def _aligned_ptr(t, V):
-  return t.data_ptr() % (V * t.element_size()) == 0
+def _ptr(t):
+  return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
 def _vec_aligned(t, strides, cls, V):
   if cls == 'c':
-    return _aligned_ptr(t, V) and all(s % V == 0 for s in strides[:-1])
+    return t.data_ptr() % (V * t.element_size()) == 0 and all(s % V == 0 for s in strides[:-1])
   return True
 
 

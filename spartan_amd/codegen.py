@@ -24,6 +24,7 @@ The source is compiled by ``backend.compile_kernel`` (device-only clang,
 code object cached on disk by source hash) and launched through the C ABI
 (spx_launch).  Nothing here executes on the CPU.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -649,6 +650,85 @@ def _acc_update(op, j, val, idx_expr):
   return 'acc%d = comb(acc%d, %s);' % (j, j, val)
 
 
+GFLAT = '''DEV i64 gflat(const KArgs& a, i64 r) {
+  i64 rem = r, g = 0, mul = 1;
+  for (int d = (int)a.aux[6] - 1; d >= 0; --d) {
+    i64 q = rem / a.tshape[d]; i64 li = rem - q * a.tshape[d]; rem = q;
+    g += (li + a.tul[d]) * mul; mul *= a.ashape[d];
+  }
+  return g;
+}'''
+
+
+class _Red:
+  """What the three reduce kernels share for one gen_reduce call: the tree,
+  its inputs and accumulator type, and the source pieces built from them."""
+
+  def __init__(self, root, inputs, classes, op, vec):
+    self.root, self.inputs, self.classes, self.op, self.vec = root, inputs, classes, op, vec
+    self.rds = rowdots(root)
+    self.adt = acc_dtype(op, root.dtype)
+    self.act = ctype(self.adt)
+    self.arg = op in ('argmin', 'argmax')
+
+  def preamble(self, kind):
+    fn, ocml = _expr_fn(self.root, self.inputs)
+    L = [PRELUDE, _ocml_decls(ocml), fn, _comb_fns(self.op, self.adt)]
+    if self.rds or kind == 'rows':
+      L += [SHFL, ROW_ALLSUM]
+    return L + [GFLAT] if self.arg else L
+
+  def update(self, j, idx_expr, sfx=''):
+    """Accumulator j takes the tree's value of the loaded element j (names suffixed sfx)."""
+    val = '(%s)%s' % (self.act, _call_expr(self.inputs, j, n_rd=len(self.rds), sfx=sfx))
+    return _acc_update(self.op, j, val, idx_expr)
+
+  def loads(self, V, base_expr, vdim):
+    b = []
+    for (s, dt), cls in zip(self.inputs, self.classes):
+      b.append('const i64 off%d = %s;' % (s, base_expr(s)))
+      if cls == 'g' and V > 1:
+        b.append('const i64 s%d_in = a.str[%d][%d];' % (s, s, vdim))
+      b += _load_vec(s, dt, cls, 'off%d' % s, V)
+    return b
+
+  def to_global(self, ind):
+    # tile-local indices of the per-thread arg accumulators -> global ones:
+    # along the reduced dim (axis) or flat (axis None)
+    if not self.arg:
+      return []
+    return [ind + 'if (acci%d != 0x7fffffffffffffffLL) acci%d = (a.aux[5] ? gflat(a, acci%d) : a.aux[4] + acci%d);'
+            % (j, j, j, j) for j in range(self.vec)]
+
+  def acc_decls(self, ind, fin=None):
+    """The vec accumulators (arg ops: and indices; fin: the type of an interleaved sum's lane totals)."""
+    L = []
+    for j in range(self.vec):
+      L.append('%s%s acc%d = %s;' % (ind, self.act, j, _ident(self.op, self.adt)))
+      if self.arg:
+        L.append('%si64 acci%d = 0x7fffffffffffffffLL;' % (ind, j))
+      if fin:
+        L.append('%s%s fin%d = 0.0;' % (ind, fin, j))
+    return L
+
+  def fold(self, ind):
+    """accv (acci) = the vec slots folded in index order."""
+    L = ['%s%s accv = acc0;' % (ind, self.act)]
+    if self.arg:
+      L.append(ind + 'i64 acci = acci0;')
+    for j in range(1, self.vec):
+      if self.arg:
+        L.append(ind + 'if (better(acc%d, acci%d, accv, acci)) { accv = acc%d; acci = acci%d; }' % (j, j, j, j))
+      else:
+        L.append(ind + 'accv = comb(accv, acc%d);' % j)
+    return L
+
+  def both_paths(self, ind, body):
+    """The vector path (flags & 1) and the scalar path of a kernel's loop."""
+    return ([ind + 'if (a.flags & 1) {'] + [ind + '  ' + x for x in body(self.vec)] + [ind + '} else {'] +
+            [ind + '  ' + x for x in body(1)] + [ind + '}'])
+
+
 def gen_reduce(root, inputs, classes, kind, op, vec, unroll=None, rowinv=(), lpr=None, full=False, interleave=False):
   """Fused map+reduce.  kind 'rows' (reduce over contiguous R of (O, R), one
   or more blocks per segment), 'rowsp' (the same for short R: several
@@ -666,420 +746,339 @@ def gen_reduce(root, inputs, classes, kind, op, vec, unroll=None, rowinv=(), lpr
   loop body was 641 instructions per 8 rows, issue-bound beside the loads.
   """
   assert op in REDOPS and kind in ('rows', 'rowsp', 'cols')
-  rds = rowdots(root)
-  if rds and kind != 'cols':
+  c = _Red(root, inputs, classes, op, vec)
+  if c.rds and kind != 'cols':
     raise NotImplementedError('a fused row dot needs the column-reduce skeleton')
-  fn, ocml = _expr_fn(root, inputs)
-  adt = acc_dtype(op, root.dtype)
-  act = ctype(adt)
-  arg = op in ('argmin', 'argmax')
-  L = [PRELUDE, _ocml_decls(ocml), fn, _comb_fns(op, adt)]
-  if rds or kind == 'rows':
-    L.append(SHFL)
-    L.append(ROW_ALLSUM)
+  if kind == 'cols':
+    kernel = _reduce_cols(c, unroll, rowinv, lpr, full, interleave)
+  else:
+    kernel = (_reduce_rows if kind == 'rows' else _reduce_rowsp)(c)
+  return '\n'.join(c.preamble(kind) + kernel)
 
-  def val_j(j):
-    return '(%s)%s' % (act, _call_expr(inputs, j, n_rd=len(rds)))
 
-  def loads(V, base_expr, vdim):
-    b = []
-    for (s, dt), cls in zip(inputs, classes):
-      b.append('const i64 off%d = %s;' % (s, base_expr(s)))
-      if cls == 'g' and V > 1:
-        b.append('const i64 s%d_in = a.str[%d][%d];' % (s, s, vdim))
-      b += _load_vec(s, dt, cls, 'off%d' % s, V)
+def _reduce_rows(c):
+  """'rows': a block per (segment, chunk) of (O, R), grid-stride over them."""
+  act, arg = c.act, c.arg
+  # U steps of the block's row loop per iteration, every load first: with
+  # one or two streamed inputs a single vector load per lane cannot keep
+  # enough bytes in flight (x.sum(axis=1) at cfg2 size: 4.1 TB/s with U=1).
+  # Each accumulator still takes its elements in the same order: results
+  # are unchanged.
+  U = rows_unroll(c.inputs, c.classes)
+
+  def body(V):
+    b = ['i64 r = r0 + (i64)tid() * %d;' % V]
+    if U > 1:
+      b.append('for (; r + %d * 256 * %d < r1; r += %d * 256 * %d) {' % (U - 1, V, U, V))
+      for u in range(U):
+        step = '(r + %d * 256 * %d)' % (u, V)
+        lines = c.loads(V, lambda s: 'o * a.str[%d][0] + %s * a.str[%d][1]' % (s, step, s), 1)
+        b += ['  ' + _suffix_names(x, '_u%d' % u) for x in lines]
+      for u in range(U):
+        for j in range(V):
+          b.append('  ' + c.update(j, '(r + %d * 256 * %d + %d)' % (u, V, j), '_u%d' % u))
+      b.append('}')
+    b.append('for (; r < r1; r += 256 * %d) {' % V)
+    b += ['  ' + x for x in c.loads(V, lambda s: 'o * a.str[%d][0] + r * a.str[%d][1]' % (s, s), 1)]
+    for j in range(V):
+      b.append('  ' + c.update(j, '(r + %d)' % j))
+    b.append('}')
     return b
 
-  def to_global():
-    # tile-local indices of the per-thread arg accumulators -> global ones
-    return ['if (acci%d != 0x7fffffffffffffffLL) acci%d = %s;' % (j, j, gidx('acci%d' % j)) for j in range(vec)]
-
-  def gidx(r_expr):
-    # global index of element r along the reduced dim (axis) or flat (axis None)
-    return ('(a.aux[5] ? gflat(a, %s) : a.aux[4] + %s)' % (r_expr, r_expr))
-
+  L = ['KERN void spx_reduce(KArgs a) {']
+  L.append('  const i64 O = a.dim[0], R = a.dim[1], P = a.aux[0], chunk = a.aux[1];')
+  # grid-stride over the O * P segments (the launch may cap the grid)
+  L.append('  for (i64 blk = bidx(); blk < O * P; blk += (i64)a.grid) {')
+  L.append('  const i64 o = blk / P, p = blk - o * P;')
+  L.append('  const i64 r0 = p * chunk; i64 r1 = r0 + chunk; if (r1 > R) r1 = R;')
+  L += c.acc_decls('  ') + c.both_paths('  ', body)
+  # in the loop the indices are tile-local (monotonic in the global index,
+  # so first-occurrence ties resolve the same); converted once here
+  L += c.to_global('  ')
+  # fold the V slots in index order, then block tree
+  L += c.fold('  ')
+  # wave level first: DPP within each 16-lane row (quad_perm [1,0,3,2],
+  # [2,3,0,1], row_half_mirror, row_mirror -- each lane meets a partner
+  # holding its mirror group's partial, and comb / better are symmetric, so
+  # every lane ends with the wave's value), ds_bpermute across rows; then
+  # the 4 wave results through LDS with one barrier (was an 8-barrier tree)
+  L.append('  const u32 t = tid();')
+  steps = ['dpp_mov<0xB1>(%s)', 'dpp_mov<0x4E>(%s)', 'dpp_mov<0x141>(%s)', 'dpp_mov<0x140>(%s)',
+           'shfl_xor(%s, 16)', 'shfl_xor(%s, 32)']
+  for st in steps:
+    if arg:
+      L.append('  { %s ov = %s; i64 oi = %s;' % (act, st % 'accv', st % 'acci'))
+      L.append('    if (better(ov, oi, accv, acci)) { accv = ov; acci = oi; } }')
+    else:
+      L.append('  accv = comb(accv, %s);' % (st % 'accv'))
+  L.append('  SHARED %s sv[4];' % act)
   if arg:
-    L.append('''DEV i64 gflat(const KArgs& a, i64 r) {
-  i64 rem = r, g = 0, mul = 1;
-  for (int d = (int)a.aux[6] - 1; d >= 0; --d) {
-    i64 q = rem / a.tshape[d]; i64 li = rem - q * a.tshape[d]; rem = q;
-    g += (li + a.tul[d]) * mul; mul *= a.ashape[d];
-  }
-  return g;
-}''')
+    L.append('  SHARED i64 si[4];')
+  L.append('  if ((t & 63) == 0) { sv[t >> 6] = accv;' + (' si[t >> 6] = acci;' if arg else '') + ' }')
+  L.append('  bsync();')
+  L.append('  if (t == 0) {')
+  L.append('    %s v = sv[0];' % act)
+  if arg:
+    L.append('    i64 vi = si[0];')
+  L.append('    for (int k = 1; k < 4; ++k) {')
+  L.append('      if (better(sv[k], si[k], v, vi)) { v = sv[k]; vi = si[k]; }' if arg else '      v = comb(v, sv[k]);')
+  L.append('    }')
+  L.append('    ((GLOBAL %s*)a.out0)[p * O + o] = v;' % act)
+  if arg:
+    L.append('    ((GLOBAL i64*)a.out1)[p * O + o] = vi;')
+  return L + ['  }', '  bsync();  // sv is rewritten by the next segment', '  }', '}']
 
-  if kind == 'rows':
-    # U steps of the block's row loop per iteration, every load first: with
-    # one or two streamed inputs a single vector load per lane cannot keep
-    # enough bytes in flight (x.sum(axis=1) at cfg2 size: 4.1 TB/s with U=1).
-    # Each accumulator still takes its elements in the same order: results
-    # are unchanged.
-    U = rows_unroll(inputs, classes)
 
-    def body(V):
-      b = []
-      b.append('i64 r = r0 + (i64)tid() * %d;' % V)
-      if U > 1:
-        b.append('for (; r + %d * 256 * %d < r1; r += %d * 256 * %d) {' % (U - 1, V, U, V))
-        for u in range(U):
-          step = '(r + %d * 256 * %d)' % (u, V)
-          lines = loads(V, lambda s: 'o * a.str[%d][0] + %s * a.str[%d][1]' % (s, step, s), 1)
-          b += ['  ' + _suffix_names(x, '_u%d' % u) for x in lines]
-        for u in range(U):
-          for j in range(V):
-            call = '(%s)%s' % (act, _call_expr(inputs, j, n_rd=len(rds), sfx='_u%d' % u))
-            b.append('  ' + _acc_update(op, j, call, '(r + %d * 256 * %d + %d)' % (u, V, j)))
-        b.append('}')
-      b.append('for (; r < r1; r += 256 * %d) {' % V)
-      b += ['  ' + x for x in loads(V, lambda s: 'o * a.str[%d][0] + r * a.str[%d][1]' % (s, s), 1)]
-      for j in range(V):
-        b.append('  ' + _acc_update(op, j, val_j(j), '(r + %d)' % j))
-      b.append('}')
-      return b
+def _reduce_rowsp(c):
+  """'rowsp': short segments of (O, R), several per wave (LPR lanes each)."""
+  act, arg = c.act, c.arg
 
-    L.append('KERN void spx_reduce(KArgs a) {')
-    L.append('  const i64 O = a.dim[0], R = a.dim[1], P = a.aux[0], chunk = a.aux[1];')
-    # grid-stride over the O * P segments (the launch may cap the grid)
-    L.append('  for (i64 blk = bidx(); blk < O * P; blk += (i64)a.grid) {')
-    L.append('  const i64 o = blk / P, p = blk - o * P;')
-    L.append('  const i64 r0 = p * chunk; i64 r1 = r0 + chunk; if (r1 > R) r1 = R;')
-    for j in range(vec):
-      L.append('  %s acc%d = %s;' % (act, j, _ident(op, adt)))
-      if arg:
-        L.append('  i64 acci%d = 0x7fffffffffffffffLL;' % j)
-    L.append('  if (a.flags & 1) {')
-    L += ['    ' + x for x in body(vec)]
-    L.append('  } else {')
-    L += ['    ' + x for x in body(1)]
-    L.append('  }')
-    # in the loop the indices are tile-local (monotonic in the global index,
-    # so first-occurrence ties resolve the same); converted once here
-    if arg:
-      L += ['  ' + x for x in to_global()]
-    # fold the V slots in index order, then block tree
-    L.append('  %s accv = acc0;' % act)
-    if arg:
-      L.append('  i64 acci = acci0;')
-    for j in range(1, vec):
-      if arg:
-        L.append('  if (better(acc%d, acci%d, accv, acci)) { accv = acc%d; acci = acci%d; }' % (j, j, j, j))
-      else:
-        L.append('  accv = comb(accv, acc%d);' % j)
-    # wave level first: DPP within each 16-lane row (quad_perm [1,0,3,2],
-    # [2,3,0,1], row_half_mirror, row_mirror -- each lane meets a partner
-    # holding its mirror group's partial, and comb / better are symmetric, so
-    # every lane ends with the wave's value), ds_bpermute across rows; then
-    # the 4 wave results through LDS with one barrier (was an 8-barrier tree)
-    L.append('  const u32 t = tid();')
-    steps = ['dpp_mov<0xB1>(%s)', 'dpp_mov<0x4E>(%s)', 'dpp_mov<0x141>(%s)', 'dpp_mov<0x140>(%s)',
-             'shfl_xor(%s, 16)', 'shfl_xor(%s, 32)']
-    for st in steps:
-      if arg:
-        L.append('  { %s ov = %s; i64 oi = %s;' % (act, st % 'accv', st % 'acci'))
-        L.append('    if (better(ov, oi, accv, acci)) { accv = ov; acci = oi; } }')
-      else:
-        L.append('  accv = comb(accv, %s);' % (st % 'accv'))
-    L.append('  SHARED %s sv[4];' % act)
-    if arg:
-      L.append('  SHARED i64 si[4];')
-    L.append('  if ((t & 63) == 0) { sv[t >> 6] = accv;' + (' si[t >> 6] = acci;' if arg else '') + ' }')
-    L.append('  bsync();')
-    L.append('  if (t == 0) {')
-    L.append('    %s v = sv[0];' % act)
-    if arg:
-      L.append('    i64 vi = si[0];')
-    L.append('    for (int k = 1; k < 4; ++k) {')
-    if arg:
-      L.append('      if (better(sv[k], si[k], v, vi)) { v = sv[k]; vi = si[k]; }')
-    else:
-      L.append('      v = comb(v, sv[k]);')
-    L.append('    }')
-    L.append('    ((GLOBAL %s*)a.out0)[p * O + o] = v;' % act)
-    if arg:
-      L.append('    ((GLOBAL i64*)a.out1)[p * O + o] = vi;')
-    L.append('  }')
-    L.append('  bsync();  // sv is rewritten by the next segment')
-    L.append('  }')
-    L.append('}')
-  elif kind == 'rowsp':
-    def body(V):
-      b = []
-      b.append('if (o < O) {')
-      b.append('  for (i64 r = cl * %d; r < R; r += LPR * %d) {' % (V, V))
-      b += ['    ' + x for x in loads(V, lambda s: 'o * a.str[%d][0] + r * a.str[%d][1]' % (s, s), 1)]
-      for j in range(V):
-        b.append('    ' + _acc_update(op, j, val_j(j), '(r + %d)' % j))
-      b.append('  }')
-      b.append('}')
-      return b
+  def body(V):
+    b = ['if (o < O) {']
+    b.append('  for (i64 r = cl * %d; r < R; r += LPR * %d) {' % (V, V))
+    b += ['    ' + x for x in c.loads(V, lambda s: 'o * a.str[%d][0] + r * a.str[%d][1]' % (s, s), 1)]
+    for j in range(V):
+      b.append('    ' + c.update(j, '(r + %d)' % j))
+    return b + ['  }', '}']
 
-    L.append(SHFL)
-    L.append('KERN void spx_reduce(KArgs a) {')
-    L.append('  const i64 O = a.dim[0], R = a.dim[1];')
-    L.append('  const i64 lpr_log = a.aux[2], LPR = (i64)1 << lpr_log, SPW = 64 >> lpr_log;')
-    L.append('  const u32 t = tid(); const i64 lane = t & 63, w = t >> 6;')
-    L.append('  const i64 sub = lane >> lpr_log, cl = lane & (LPR - 1);')
-    L.append('  const i64 step = (i64)a.grid * 4 * SPW;')
-    L.append('  for (i64 sb = (i64)bidx() * 4 * SPW; sb < O; sb += step) {')
-    L.append('    const i64 o = sb + w * SPW + sub;')
-    for j in range(vec):
-      L.append('    %s acc%d = %s;' % (act, j, _ident(op, adt)))
-      if arg:
-        L.append('    i64 acci%d = 0x7fffffffffffffffLL;' % j)
-    L.append('    if (a.flags & 1) {')
-    L += ['      ' + x for x in body(vec)]
-    L.append('    } else {')
-    L += ['      ' + x for x in body(1)]
-    L.append('    }')
-    if arg:
-      L += ['    ' + x for x in to_global()]
-    L.append('    %s accv = acc0;' % act)
-    if arg:
-      L.append('    i64 acci = acci0;')
-    for j in range(1, vec):
-      if arg:
-        L.append('    if (better(acc%d, acci%d, accv, acci)) { accv = acc%d; acci = acci%d; }' % (j, j, j, j))
-      else:
-        L.append('    accv = comb(accv, acc%d);' % j)
-    L.append('    for (i64 m = 1; m < LPR; m <<= 1) {')
-    L.append('      %s ov = shfl_xor(accv, (int)m);' % act)
-    if arg:
-      L.append('      i64 oi = shfl_xor(acci, (int)m);')
-      L.append('      if (better(ov, oi, accv, acci)) { accv = ov; acci = oi; }')
-    else:
-      L.append('      accv = (cl & m) ? comb(ov, accv) : comb(accv, ov);')
-    L.append('    }')
-    L.append('    if (cl == 0 && o < O) {')
-    L.append('      ((GLOBAL %s*)a.out0)[o] = accv;' % act)
-    if arg:
-      L.append('      ((GLOBAL i64*)a.out1)[o] = acci;')
-    L.append('    }')
-    L.append('  }')
-    L.append('}')
+  L = [SHFL, 'KERN void spx_reduce(KArgs a) {']
+  L.append('  const i64 O = a.dim[0], R = a.dim[1];')
+  L.append('  const i64 lpr_log = a.aux[2], LPR = (i64)1 << lpr_log, SPW = 64 >> lpr_log;')
+  L.append('  const u32 t = tid(); const i64 lane = t & 63, w = t >> 6;')
+  L.append('  const i64 sub = lane >> lpr_log, cl = lane & (LPR - 1);')
+  L.append('  const i64 step = (i64)a.grid * 4 * SPW;')
+  L.append('  for (i64 sb = (i64)bidx() * 4 * SPW; sb < O; sb += step) {')
+  L.append('    const i64 o = sb + w * SPW + sub;')
+  L += c.acc_decls('    ') + c.both_paths('    ', body) + c.to_global('    ') + c.fold('    ')
+  L.append('    for (i64 m = 1; m < LPR; m <<= 1) {')
+  L.append('      %s ov = shfl_xor(accv, (int)m);' % act)
+  if arg:
+    L.append('      i64 oi = shfl_xor(acci, (int)m);')
+    L.append('      if (better(ov, oi, accv, acci)) { accv = ov; acci = oi; }')
   else:
-    U = unroll or cols_unroll(inputs, classes, vec)
-    lv = interleave and op == 'sum'
-    pact = ctype(partial_dtype(op, adt, interleave))
-    kahan = lv and pact == 'double' and act == 'double'
+    L.append('      accv = (cl & m) ? comb(ov, accv) : comb(accv, ov);')
+  L.append('    }')
+  L.append('    if (cl == 0 && o < O) {')
+  L.append('      ((GLOBAL %s*)a.out0)[o] = accv;' % act)
+  if arg:
+    L.append('      ((GLOBAL i64*)a.out1)[o] = acci;')
+  return L + ['    }', '  }', '}']
 
-    def one_row(V, rv, sfx, masked, bcu=None):
-      """Loads + (row dots) + accumulator updates of row ``rv`` into names
-      suffixed ``sfx``; split in (load lines, compute lines) so an unrolled
-      body issues every row's loads before the first use.  ``bcu``: this
-      row's index u in an unrolled step whose per-row ('b') inputs were loaded
-      once, row u by lane u of the 16-lane group (``yb<s>``): the value comes
-      by DPP row_newbcast:u instead of a load per row."""
-      ld, cp = [], []
-      base = lambda s, c: 'o * a.str[%d][0] + %s * a.str[%d][1] + %s * a.str[%d][2]' % (s, rv, s, c, s)
-      for (s, dt), cls in zip(inputs, classes):
-        ct = ctype(dt)
-        names = ['x%d_%d%s' % (s, j, sfx) for j in range(V)]
-        if s in rowinv:
-          ld += ['%s %s = x%d_%d_ri;' % (ct, n, s, j) for j, n in enumerate(names)]
-          continue
-        if bcu is not None and s in bcast:
-          # (with the compute lines: the broadcast waits for the one load,
-          # which must not hold back the rows' loads)
-          v = 'dpp_mov<%d>(yb%d)' % (0x150 + bcu, s)
-          cp.append('const %s xbb%d%s = %s;' % (ct, s, sfx, v))
-          cp += ['%s %s = %s;' % (ct, n, ('colok ? xbb%d%s : (%s)0' % (s, sfx, ct)) if masked else 'xbb%d%s' % (s, sfx))
-                 for n in names]
-          continue
-        srcs, pre = load_srcs(s, dt, cls, V, base(s, 'cc' if masked else 'col'))
-        ld.append('%s %s;' % (ct, ' '.join(names).replace(' ', ', ')))
-        ld.append('{')
-        ld += ['  ' + x for x in pre]
-        # masked lanes load column 0 (always in bounds) and select zero at use
-        ld += ['  %s = %s;' % (n, ('colok ? %s : (%s)0' % (v, ct)) if masked else v) for n, v in zip(names, srcs)]
-        ld.append('}')
-      for rd in rds:
-        ct = ctype(rd.dtype)
-        n = 'rd%d%s' % (rd.rid, sfx)
-        cp.append('%s %s = (%s)0;' % (ct, n, ct))
-        for j in range(V):
-          cp.append('%s = %s + (%s)x%d_%d%s * (%s)x%d_%d%s;' % (n, n, ct, rd.a.slot, j, sfx, ct, rd.w.slot, j, sfx))
-        cp.append('%s = row_allsum(%s, LPR);' % (n, n))
-      upd = []
-      for j in range(V):
-        call = '(%s)%s' % (act, _call_expr(inputs, j, n_rd=len(rds), sfx=sfx))
-        upd.append(_acc_update(op, j, call, '(%s)' % rv))
-      if masked:
-        cp.append('if (colok) {')
-        cp += ['  ' + x for x in upd]
-        cp.append('}')
-      else:
-        cp += upd
-      return ld, cp
 
-    def load_srcs(s, dt, cls, V, off):
-      """(per-element source expressions, preamble lines) of one vector load."""
+# 'cols': blocks over (column tile, O, row chunk) of (O, R, I), lanes along I.
+# _Cols: what gen_reduce was given for it and what follows from that.
+_Cols = collections.namedtuple('_Cols', 'U rowinv lpr full interleave lv pact kahan bcast')
+
+
+def _cols_load_srcs(s, dt, cls, V, off):
+  """(per-element source expressions, preamble lines) of one vector load."""
+  ct = ctype(dt)
+  p = '((const GLOBAL %s*)a.ptr[%d])' % (ct, s)
+  pre = ['const i64 off = %s;' % off]
+  if V > 1 and cls == 'c':
+    pre.append('typedef %s __attribute__((ext_vector_type(%d))) vt;' % (ct, V))
+    pre.append('const vt xv = %s;' % _vload('vt', '%s + off' % p))
+    return ['xv[%d]' % j for j in range(V)], pre
+  if V > 1 and cls == 'b':
+    pre.append('const %s xb = %s[off];' % (ct, p))
+    return ['xb'] * V, pre
+  if V > 1:
+    pre.append('const i64 s_in = a.str[%d][2];' % s)
+    return ['%s[off + %d * s_in]' % (p, j) for j in range(V)], pre
+  return ['%s[off]' % p], pre
+
+
+def _cols_one_row(c, k, V, rv, sfx, masked, bcu=None):
+  """Loads + (row dots) + accumulator updates of row ``rv`` into names
+  suffixed ``sfx``; split in (load lines, compute lines) so an unrolled
+  body issues every row's loads before the first use.  ``bcu``: this
+  row's index u in an unrolled step whose per-row ('b') inputs were loaded
+  once, row u by lane u of the 16-lane group (``yb<s>``): the value comes
+  by DPP row_newbcast:u instead of a load per row."""
+  ld, cp = [], []
+  base = lambda s, col: 'o * a.str[%d][0] + %s * a.str[%d][1] + %s * a.str[%d][2]' % (s, rv, s, col, s)
+  for (s, dt), cls in zip(c.inputs, c.classes):
+    ct = ctype(dt)
+    names = ['x%d_%d%s' % (s, j, sfx) for j in range(V)]
+    if s in k.rowinv:
+      ld += ['%s %s = x%d_%d_ri;' % (ct, n, s, j) for j, n in enumerate(names)]
+      continue
+    if bcu is not None and s in k.bcast:
+      # (with the compute lines: the broadcast waits for the one load,
+      # which must not hold back the rows' loads)
+      v = 'dpp_mov<%d>(yb%d)' % (0x150 + bcu, s)
+      cp.append('const %s xbb%d%s = %s;' % (ct, s, sfx, v))
+      cp += ['%s %s = %s;' % (ct, n, ('colok ? xbb%d%s : (%s)0' % (s, sfx, ct)) if masked else 'xbb%d%s' % (s, sfx))
+             for n in names]
+      continue
+    srcs, pre = _cols_load_srcs(s, dt, cls, V, base(s, 'cc' if masked else 'col'))
+    ld.append('%s %s;' % (ct, ' '.join(names).replace(' ', ', ')))
+    ld.append('{')
+    ld += ['  ' + x for x in pre]
+    # masked lanes load column 0 (always in bounds) and select zero at use
+    ld += ['  %s = %s;' % (n, ('colok ? %s : (%s)0' % (v, ct)) if masked else v) for n, v in zip(names, srcs)]
+    ld.append('}')
+  for rd in c.rds:
+    ct = ctype(rd.dtype)
+    n = 'rd%d%s' % (rd.rid, sfx)
+    cp.append('%s %s = (%s)0;' % (ct, n, ct))
+    for j in range(V):
+      cp.append('%s = %s + (%s)x%d_%d%s * (%s)x%d_%d%s;' % (n, n, ct, rd.a.slot, j, sfx, ct, rd.w.slot, j, sfx))
+    cp.append('%s = row_allsum(%s, LPR);' % (n, n))
+  upd = [c.update(j, '(%s)' % rv, sfx) for j in range(V)]
+  if masked:
+    cp += ['if (colok) {'] + ['  ' + x for x in upd] + ['}']
+  else:
+    cp += upd
+  return ld, cp
+
+
+def _cols_body(c, k, V):
+  """The row loop of one path (vector width V) of the 'cols' kernel."""
+  U, act, pact = k.U, c.act, k.pact
+  masked = bool(c.rds)
+  # row-dot kernels: every lane of a row group takes part in the DPP row
+  # sum, so lanes past the last column read column 0 and use zeros
+  b = ['{' if masked else 'if (col < I) {']
+  b.append('  const bool colok = %s; (void)colok;' % ('true' if (k.full and k.lpr and V == c.vec) else 'col < I'))
+  b.append('  const i64 cc = colok ? col : 0; (void)cc;')
+  for (s, dt), cls in zip(c.inputs, c.classes):
+    if s in k.rowinv:  # row stride 0: loaded once, outside the row loop
       ct = ctype(dt)
-      p = '((const GLOBAL %s*)a.ptr[%d])' % (ct, s)
-      pre = ['const i64 off = %s;' % off]
-      if V > 1 and cls == 'c':
-        pre.append('typedef %s __attribute__((ext_vector_type(%d))) vt;' % (ct, V))
-        pre.append('const vt xv = %s;' % _vload('vt', '%s + off' % p))
-        return ['xv[%d]' % j for j in range(V)], pre
-      if V > 1 and cls == 'b':
-        pre.append('const %s xb = %s[off];' % (ct, p))
-        return ['xb'] * V, pre
-      if V > 1:
-        pre.append('const i64 s_in = a.str[%d][2];' % s)
-        return ['%s[off + %d * s_in]' % (p, j) for j in range(V)], pre
-      return ['%s[off]' % p], pre
-
-    # per-row inputs of a row-dot kernel with 16-lane row groups: one load per
-    # unrolled step (lane u of the group fetches row u), DPP broadcasts --
-    # for 4- and 8-byte values only (dpp_mov moves one or two dwords; a bool,
-    # int8 or fp16 row input keeps its per-row load)
-    bcast = ()
-    if rds and lpr == 16 and U > 1 and U <= 16:
-      bcast = tuple(s for (s, dt), cls in zip(inputs, classes)
-                    if cls == 'b' and s not in rowinv and np.dtype(dt).itemsize in (4, 8))
-
-    def body(V):
-      masked = bool(rds)
-      b = []
-      # row-dot kernels: every lane of a row group takes part in the DPP row
-      # sum, so lanes past the last column read column 0 and use zeros
-      b.append('{' if masked else 'if (col < I) {')
-      b.append('  const bool colok = %s; (void)colok;' % ('true' if (full and lpr and V == vec) else 'col < I'))
-      b.append('  const i64 cc = colok ? col : 0; (void)cc;')
-      for (s, dt), cls in zip(inputs, classes):
-        if s in rowinv:  # row stride 0: loaded once, outside the row loop
-          ct = ctype(dt)
-          srcs, pre = load_srcs(s, dt, cls, V, 'o * a.str[%d][0] + %s * a.str[%d][2]'
-                                % (s, 'cc' if masked else 'col', s))
-          b.append('  %s %s;' % (ct, ', '.join('x%d_%d_ri' % (s, j) for j in range(V))))
-          b.append('  {')
-          b += ['    ' + x for x in pre]
-          b += ['    x%d_%d_ri = %s;' % (s, j, (('colok ? %s : (%s)0' % (v, ct)) if masked else v))
-                for j, v in enumerate(srcs)]
-          b.append('  }')
-      b.append('  const i64 STEP = 4 * RPW;')
-      if interleave:
-        # block p takes the U-step super-chunks p, p + P, p + 2P, ...: at any
-        # moment the grid streams one contiguous stretch of X instead of P
-        # streams far apart (one chunk per block).  A block then covers R / P
-        # rows, so (sums) each super-chunk's U rows go into a fresh
-        # accumulator (in the input's precision: U additions) that is folded
-        # into a middle one, and every 32 chunks the middle one into the
-        # block's total.  Middle and total are fp64 (round 6; fp32 inputs:
-        # only the U-row chunk sums round to fp32, everything above them --
-        # lane total, LDS combine, partials, finalize -- is fp64), and for
-        # fp64 inputs the total is Kahan-compensated (topc)
-        if lv:
-          b.append('  %s %s;' % (pact, ', '.join('mid%d = 0.0, top%d = 0.0' % (j, j) for j in range(V))))
-          if kahan:
-            b.append('  double %s;' % ', '.join('topc%d = 0.0' % j for j in range(V)))
-          b.append('  int nsc = 0;')
-        b.append('  for (i64 sb = p * (%d * STEP); sb < R; sb += P * (%d * STEP)) {' % (U, U))
-        b.append('  const i64 r0 = sb; i64 r1 = sb + %d * STEP; if (r1 > R) r1 = R;' % U)
-      b.append('  i64 r = r0 + w * RPW + sub;')
-      if U > 1:
-        b.append('  for (; r + %d * STEP < r1; r += %d * STEP) {' % (U - 1, U))
-        lds, cps = [], []
-        for s_ in bcast:
-          ct = ctype(dict(inputs)[s_])
-          b.append('    %s yb%d;' % (ct, s_))
-          b.append('    { const i64 rb = r + (cl < %d ? cl : 0) * STEP;' % U)
-          b.append('      yb%d = ((const GLOBAL %s*)a.ptr[%d])[o * a.str[%d][0] + rb * a.str[%d][1]]; }'
-                   % (s_, ct, s_, s_, s_))
-        for u in range(U):
-          b.append('    const i64 r_%d = r + %d * STEP;' % (u, u))
-          ld, cp = one_row(V, 'r_%d' % u, '_u%d' % u, masked, u if bcast else None)
-          lds += ld
-          cps += cp
-        b += ['    ' + x for x in lds + cps]
-        b.append('  }')
-      b.append('  for (; r < r1; r += STEP) {')
-      ld, cp = one_row(V, 'r', '', masked)
-      b += ['    ' + x for x in ld + cp]
+      srcs, pre = _cols_load_srcs(s, dt, cls, V, 'o * a.str[%d][0] + %s * a.str[%d][2]'
+                                  % (s, 'cc' if masked else 'col', s))
+      b.append('  %s %s;' % (ct, ', '.join('x%d_%d_ri' % (s, j) for j in range(V))))
+      b.append('  {')
+      b += ['    ' + x for x in pre]
+      b += ['    x%d_%d_ri = %s;' % (s, j, (('colok ? %s : (%s)0' % (v, ct)) if masked else v))
+            for j, v in enumerate(srcs)]
       b.append('  }')
-      if interleave:
-        if lv:
-          for j in range(V):
-            b.append('  mid%d = mid%d + (%s)acc%d; acc%d = (%s)0;' % (j, j, pact, j, j, act))
-          b.append('  if (++nsc == 32) {')
-          for j in range(V):
-            if kahan:
-              b.append('    { const double y_ = mid%d - topc%d, t_ = top%d + y_; topc%d = (t_ - top%d) - y_; '
-                       'top%d = t_; } mid%d = 0.0;' % (j, j, j, j, j, j, j))
-            else:
-              b.append('    top%d = top%d + mid%d; mid%d = 0.0;' % (j, j, j, j))
-          b.append('    nsc = 0;')
-          b.append('  }')
-        b.append('  }')
-        if lv:
-          for j in range(V):
-            if kahan:
-              b.append('  fin%d = top%d + (mid%d - topc%d);' % (j, j, j, j))
-            else:
-              b.append('  fin%d = top%d + mid%d;' % (j, j, j))
-      b.append('}')
-      return b
+  b.append('  const i64 STEP = 4 * RPW;')
+  if k.interleave:
+    # block p takes the U-step super-chunks p, p + P, p + 2P, ...: at any
+    # moment the grid streams one contiguous stretch of X instead of P
+    # streams far apart (one chunk per block).  A block then covers R / P
+    # rows, so (sums) each super-chunk's U rows go into a fresh
+    # accumulator (in the input's precision: U additions) that is folded
+    # into a middle one, and every 32 chunks the middle one into the
+    # block's total.  Middle and total are fp64 (round 6; fp32 inputs:
+    # only the U-row chunk sums round to fp32, everything above them --
+    # lane total, LDS combine, partials, finalize -- is fp64), and for
+    # fp64 inputs the total is Kahan-compensated (topc)
+    if k.lv:
+      b.append('  %s %s;' % (pact, ', '.join('mid%d = 0.0, top%d = 0.0' % (j, j) for j in range(V))))
+      if k.kahan:
+        b.append('  double %s;' % ', '.join('topc%d = 0.0' % j for j in range(V)))
+      b.append('  int nsc = 0;')
+    b.append('  for (i64 sb = p * (%d * STEP); sb < R; sb += P * (%d * STEP)) {' % (U, U))
+    b.append('  const i64 r0 = sb; i64 r1 = sb + %d * STEP; if (r1 > R) r1 = R;' % U)
+  b.append('  i64 r = r0 + w * RPW + sub;')
+  if U > 1:
+    b.append('  for (; r + %d * STEP < r1; r += %d * STEP) {' % (U - 1, U))
+    lds, cps = [], []
+    for s_ in k.bcast:
+      ct = ctype(dict(c.inputs)[s_])
+      b.append('    %s yb%d;' % (ct, s_))
+      b.append('    { const i64 rb = r + (cl < %d ? cl : 0) * STEP;' % U)
+      b.append('      yb%d = ((const GLOBAL %s*)a.ptr[%d])[o * a.str[%d][0] + rb * a.str[%d][1]]; }'
+               % (s_, ct, s_, s_, s_))
+    for u in range(U):
+      b.append('    const i64 r_%d = r + %d * STEP;' % (u, u))
+      ld, cp = _cols_one_row(c, k, V, 'r_%d' % u, '_u%d' % u, masked, u if k.bcast else None)
+      lds += ld
+      cps += cp
+    b += ['    ' + x for x in lds + cps]
+    b.append('  }')
+  b.append('  for (; r < r1; r += STEP) {')
+  ld, cp = _cols_one_row(c, k, V, 'r', '', masked)
+  b += ['    ' + x for x in ld + cp]
+  b.append('  }')
+  if k.interleave:
+    if k.lv:
+      for j in range(V):
+        b.append('  mid%d = mid%d + (%s)acc%d; acc%d = (%s)0;' % (j, j, pact, j, j, act))
+      b.append('  if (++nsc == 32) {')
+      for j in range(V):
+        if k.kahan:
+          b.append('    { const double y_ = mid%d - topc%d, t_ = top%d + y_; topc%d = (t_ - top%d) - y_; '
+                   'top%d = t_; } mid%d = 0.0;' % (j, j, j, j, j, j, j))
+        else:
+          b.append('    top%d = top%d + mid%d; mid%d = 0.0;' % (j, j, j, j))
+      b.append('    nsc = 0;')
+      b.append('  }')
+    b.append('  }')
+    if k.lv:
+      for j in range(V):
+        if k.kahan:
+          b.append('  fin%d = top%d + (mid%d - topc%d);' % (j, j, j, j))
+        else:
+          b.append('  fin%d = top%d + mid%d;' % (j, j, j))
+  b.append('}')
+  return b
 
-    L.append('KERN void spx_reduce(KArgs a) {')
-    L.append('  const i64 O = a.dim[0], R = a.dim[1], I = a.dim[2];')
-    if lpr:
-      assert lpr & (lpr - 1) == 0 and 1 <= lpr <= 64
-      L.append('  const i64 P = a.aux[0], chunk = a.aux[1], CT = a.aux[3];')
-      L.append('  constexpr i64 lpr_log = %d, LPR = %d, RPW = %d;' % (lpr.bit_length() - 1, lpr, 64 // lpr))
-    else:
-      L.append('  const i64 P = a.aux[0], chunk = a.aux[1], lpr_log = a.aux[2], CT = a.aux[3];')
-      L.append('  const i64 LPR = (i64)1 << lpr_log, RPW = 64 >> lpr_log;')
-    L.append('  const i64 blk = bidx(); const i64 ct = blk % CT; const i64 rest = blk / CT;')
-    L.append('  const i64 o = rest % O, p = rest / O;')
-    L.append('  const u32 t = tid(); const i64 lane = t & 63, w = t >> 6;')
-    L.append('  const i64 sub = lane >> lpr_log, cl = lane & (LPR - 1);')
-    L.append('  const i64 V = (a.flags & 1) ? %d : 1;' % vec)
-    L.append('  const i64 col = ct * (LPR * V) + cl * V;')
-    L.append('  const i64 r0 = p * chunk; i64 r1 = r0 + chunk; if (r1 > R) r1 = R;')
-    for j in range(vec):
-      L.append('  %s acc%d = %s;' % (act, j, _ident(op, adt)))
-      if arg:
-        L.append('  i64 acci%d = 0x7fffffffffffffffLL;' % j)
-      if lv:
-        L.append('  %s fin%d = 0.0;' % (pact, j))
-    L.append('  if (a.flags & 1) {')
-    L += ['    ' + x for x in body(vec)]
-    L.append('  } else {')
-    L += ['    ' + x for x in body(1)]
-    L.append('  }')
-    if arg:
-      L += ['  ' + x for x in to_global()]
-    # LDS combine over the 4*RPW row groups sharing a column, in row-group
-    # order (in the partials' type: fp64 for an interleaved fp32 sum)
-    L.append('  SHARED %s sv[256 * %d];' % (pact, vec))
-    if arg:
-      L.append('  SHARED i64 si[256 * %d];' % vec)
-    L.append('  const i64 grp = w * RPW + sub;')
-    L.append('  const i64 W = LPR * V;')
-    for j in range(vec):
-      L.append('  if (%d < V) { sv[grp * W + cl * V + %d] = %s%d;%s }'
-               % (j, j, 'fin' if lv else 'acc', j, (' si[grp * W + cl * V + %d] = acci%d;' % (j, j)) if arg else ''))
-    L.append('  bsync();')
-    L.append('  if ((i64)t < W) {')
-    L.append('    %s b = sv[t];' % pact)
-    if arg:
-      L.append('    i64 bi = si[t];')
-    L.append('    for (i64 g = 1; g < 4 * RPW; ++g) {')
-    if arg:
-      L.append('      if (better(sv[g * W + t], si[g * W + t], b, bi)) { b = sv[g * W + t]; bi = si[g * W + t]; }')
-    elif lv:
-      L.append('      b = b + sv[g * W + t];')
-    else:
-      L.append('      b = comb(b, sv[g * W + t]);')
-    L.append('    }')
-    L.append('    const i64 gc = ct * W + t;')
-    L.append('    if (gc < I) {')
-    L.append('      ((GLOBAL %s*)a.out0)[(p * O + o) * I + gc] = b;' % pact)
-    if arg:
-      L.append('      ((GLOBAL i64*)a.out1)[(p * O + o) * I + gc] = bi;')
-    L.append('    }')
-    L.append('  }')
-    L.append('}')
-  return '\n'.join(L)
+
+def _reduce_cols(c, unroll, rowinv, lpr, full, interleave):
+  """'cols': the block's 4 * RPW row groups stride over its chunk of R, LDS combine."""
+  act, arg, vec = c.act, c.arg, c.vec
+  U = unroll or cols_unroll(c.inputs, c.classes, vec)
+  lv = interleave and c.op == 'sum'
+  pact = ctype(partial_dtype(c.op, c.adt, interleave))
+  # per-row inputs of a row-dot kernel with 16-lane row groups: one load per
+  # unrolled step (lane u of the group fetches row u), DPP broadcasts --
+  # for 4- and 8-byte values only (dpp_mov moves one or two dwords; a bool,
+  # int8 or fp16 row input keeps its per-row load)
+  bcast = ()
+  if c.rds and lpr == 16 and U > 1 and U <= 16:
+    bcast = tuple(s for (s, dt), cls in zip(c.inputs, c.classes)
+                  if cls == 'b' and s not in rowinv and np.dtype(dt).itemsize in (4, 8))
+  k = _Cols(U, rowinv, lpr, full, interleave, lv, pact, lv and pact == 'double' and act == 'double', bcast)
+  L = ['KERN void spx_reduce(KArgs a) {']
+  L.append('  const i64 O = a.dim[0], R = a.dim[1], I = a.dim[2];')
+  if lpr:
+    assert lpr & (lpr - 1) == 0 and 1 <= lpr <= 64
+    L.append('  const i64 P = a.aux[0], chunk = a.aux[1], CT = a.aux[3];')
+    L.append('  constexpr i64 lpr_log = %d, LPR = %d, RPW = %d;' % (lpr.bit_length() - 1, lpr, 64 // lpr))
+  else:
+    L.append('  const i64 P = a.aux[0], chunk = a.aux[1], lpr_log = a.aux[2], CT = a.aux[3];')
+    L.append('  const i64 LPR = (i64)1 << lpr_log, RPW = 64 >> lpr_log;')
+  L.append('  const i64 blk = bidx(); const i64 ct = blk % CT; const i64 rest = blk / CT;')
+  L.append('  const i64 o = rest % O, p = rest / O;')
+  L.append('  const u32 t = tid(); const i64 lane = t & 63, w = t >> 6;')
+  L.append('  const i64 sub = lane >> lpr_log, cl = lane & (LPR - 1);')
+  L.append('  const i64 V = (a.flags & 1) ? %d : 1;' % vec)
+  L.append('  const i64 col = ct * (LPR * V) + cl * V;')
+  L.append('  const i64 r0 = p * chunk; i64 r1 = r0 + chunk; if (r1 > R) r1 = R;')
+  L += c.acc_decls('  ', pact if lv else None)
+  L += c.both_paths('  ', lambda V: _cols_body(c, k, V)) + c.to_global('  ')
+  # LDS combine over the 4*RPW row groups sharing a column, in row-group
+  # order (in the partials' type: fp64 for an interleaved fp32 sum)
+  L.append('  SHARED %s sv[256 * %d];' % (pact, vec))
+  if arg:
+    L.append('  SHARED i64 si[256 * %d];' % vec)
+  L.append('  const i64 grp = w * RPW + sub;')
+  L.append('  const i64 W = LPR * V;')
+  for j in range(vec):
+    L.append('  if (%d < V) { sv[grp * W + cl * V + %d] = %s%d;%s }'
+             % (j, j, 'fin' if lv else 'acc', j, (' si[grp * W + cl * V + %d] = acci%d;' % (j, j)) if arg else ''))
+  L.append('  bsync();')
+  L.append('  if ((i64)t < W) {')
+  L.append('    %s b = sv[t];' % pact)
+  if arg:
+    L.append('    i64 bi = si[t];')
+  L.append('    for (i64 g = 1; g < 4 * RPW; ++g) {')
+  if arg:
+    L.append('      if (better(sv[g * W + t], si[g * W + t], b, bi)) { b = sv[g * W + t]; bi = si[g * W + t]; }')
+  elif lv:
+    L.append('      b = b + sv[g * W + t];')
+  else:
+    L.append('      b = comb(b, sv[g * W + t]);')
+  L.append('    }')
+  L.append('    const i64 gc = ct * W + t;')
+  L.append('    if (gc < I) {')
+  L.append('      ((GLOBAL %s*)a.out0)[(p * O + o) * I + gc] = b;' % pact)
+  if arg:
+    L.append('      ((GLOBAL i64*)a.out1)[(p * O + o) * I + gc] = bi;')
+  return L + ['    }', '  }', '}']
 
 
 SHFL = r'''

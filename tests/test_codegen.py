@@ -64,6 +64,16 @@ def test_generated_source_is_deterministic():
   assert a == b and backend.source_key(a) == backend.source_key(b)
 
 
+@pytest.mark.parametrize('kind', ['rows', 'rowsp', 'cols'])
+@pytest.mark.parametrize('op', codegen.REDOPS)
+def test_reduce_source_has_one_entry(kind, op):
+  """codegen.named() renames the one ``KERN void spx_reduce(`` of a generated
+  source: every per-kind generator emits exactly one."""
+  src = codegen.gen_reduce(Op('multiply', [In(0, F32), In(1, F32)]), [(0, F32), (1, F32)], ['c', 'b'], kind, op, 4)
+  assert src.count('KERN void spx_reduce(') == 1
+  assert codegen.named(src, 'spx_reduce', kind)[1].startswith('spx_reduce_%s_' % kind)
+
+
 @pytest.mark.parametrize('dt', [F32, F64])
 def test_rowdot_cols_compile(dt):
   """DotReduceFusion's row-dot leaf in the column-reduce skeleton (vector and

@@ -702,6 +702,66 @@ def test_replayed_plans_follow_new_values(ex, W):
   assert be._reduce_plans  # the replay path was taken
 
 
+def _backend_reduce(be, t, op, axis):
+  """backend.reduce of the fp32 device tensor ``t`` itself (no expr layer)
+  as a NumPy array; arg ops: the indices."""
+  from spartan_amd import codegen
+  shape = tuple(t.shape)
+  oshape = () if axis is None else shape[:axis] + shape[axis + 1:]
+  arg = op in ('argmin', 'argmax')
+  r = be.reduce(codegen.In(0, np.float32), op, {0: t}, shape, axis, oshape, np.int64 if arg else np.float32,
+                {'offset': 0} if arg else None)
+  return (r[1] if arg else r).cpu().numpy()
+
+
+@pytest.mark.parametrize('shape,axis,op,kind,grid', [((3, 5000), 1, 'sum', 'rows', 3 * 2),
+                                                     ((5000, 8), 0, 'sum', 'cols', 10),
+                                                     ((5000, 8), 0, 'argmin', 'cols', 10)])
+def test_reduce_first_call_and_replay_identical(ex, shape, axis, op, kind, grid):
+  """One executor launches a planned reduction on its first call and on every
+  replay: both results are bit-identical and match NumPy, and the replay adds
+  neither a launch plan nor a kernel.  grid = segments x P partials each
+  (P = 2 / 10: the finalize pass runs)."""
+  import torch
+  from spartan_amd import backend
+  ex[1](1)
+  be = backend.get()
+  X = rng.rand(shape, 77, np.float32) - np.float32(0.5)
+  t = torch.as_tensor(X).cuda()
+  be._reduce_plans.clear()
+  be.launch_log = []
+  try:
+    first = _backend_reduce(be, t, op, axis)
+    counts = (len(be._reduce_plans), len(be._sig_fns), len(be._fns))
+    again = _backend_reduce(be, t, op, axis)
+    assert be.launch_log == [grid, grid]
+  finally:
+    be.launch_log = None
+  assert counts[0] == 1 and (len(be._reduce_plans), len(be._sig_fns), len(be._fns)) == counts
+  assert [k for k in be._sig_fns if k[0] == 'reduce' and k[4:6] == (kind, op)]
+  np.testing.assert_array_equal(first, again)
+  if op == 'argmin':
+    np.testing.assert_array_equal(first, X.argmin(axis))
+  else:
+    check_fp(first, X.sum(axis), X.astype(np.float64).sum(axis), 1e-5)
+
+
+def test_reduce_strided_view_twice(ex):
+  """A strided view whose dims do not collapse to (O, R, I) is copied dense on
+  every call: the second call of the same view must not relaunch the copy's
+  plan on the view's own pointer."""
+  import torch
+  from spartan_amd import backend
+  ex[1](1)
+  be = backend.get()
+  X = rng.rand((6, 10, 8), 78, np.float32)
+  v = torch.as_tensor(X).cuda()[:, ::2, ::2]
+  for axis in (None, 0):
+    first, again = _backend_reduce(be, v, 'sum', axis), _backend_reduce(be, v, 'sum', axis)
+    np.testing.assert_array_equal(first, again)
+    check_fp(first, X[:, ::2, ::2].sum(axis), X[:, ::2, ::2].astype(np.float64).sum(axis), 1e-5)
+
+
 def _rowdot_exact(X, w, Yv):
   """(sum(x * (x w - y), axis=0), x w - y) as float64 arrays, computed in
   float64 for fp32 inputs and in extended precision (np.longdouble, 64-bit
