@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 #define SPX_ABI_VERSION 3  /* 2: spx_kmeans_assign dist_dtype; collectives; 3: spx_kmeans_step */
-/* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan */
+/* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan,
+ * spx_sort_workspace, spx_sort, spx_sort_plan */
 
 /* error codes */
 #define SPX_OK 0
@@ -263,6 +264,42 @@ int64_t spx_scan_workspace(int in_dtype, int64_t outer, int64_t n, int64_t inner
 int spx_scan(int in_dtype, const void* in, void* out, int64_t outer, int64_t n, int64_t inner,
              const void* carry, void* totals, int exclusive, void* workspace, size_t workspace_bytes,
              void* stream);
+
+/* ---------------------------------------------------------- sort / argsort
+ * np.sort / np.argsort(kind='stable') along one axis of a tile: the per-tile
+ * _sort_mapper / _argsort_mapper of spartan/expr/sort.py:78-91.  `in` is a
+ * dense row-major block viewed as (outer, n, inner), as in spx_scan; each of
+ * the outer * inner lines is sorted ascending along n.  Additive since ABI 3.
+ *   out_vals  NULL, or in's dtype: the sorted values;
+ *   out_idx   NULL, or int64: the positions 0..n-1 within the line (argsort);
+ *             both NULL: SPX_EINVAL.  `in` may not alias an output.
+ * dtypes BOOL / I32 / I64 / F32 / F64.  The sort is STABLE and keys compare
+ * as NumPy compares them: integers signed, bool 0 < 1, -0.0 == +0.0 (zeros tie
+ * and keep input order), every NaN ties with every other NaN and sorts after
+ * +inf.  So out_idx is np.argsort(x, axis=1, kind='stable') bit for bit and
+ * in[out_idx] along the line is out_vals.  out_vals is a permutation of the
+ * line's bit patterns (the signs of zeros included) except that NaNs, which
+ * come last, have their sign and payload canonicalised.
+ * Lines of n <= 2048 are sorted in LDS (one read, one write, no workspace);
+ * longer lines take least-significant-digit radix passes of 8 bits (1 / 4 /
+ * 8 passes for BOOL / 32-bit / 64-bit keys), three launches each (per-tile
+ * digit counts, their exclusive scan, a stable scatter), ping-ponging between
+ * two buffers in the workspace; strided lines (inner > 1) are transposed into
+ * the workspace before the passes and back into the outputs after them (two
+ * more passes over the data).  No launch has one workgroup wait for another;
+ * no float atomics; the same input and geometry give the same bits.
+ * workspace_bytes must be at least spx_sort_workspace(dtype, outer, n, inner,
+ * out_idx != NULL) (0 for the LDS path; < 0 on bad arguments).  Arguments are
+ * checked before any device work: SPX_EINVAL for null / negative arguments,
+ * an unknown dtype or a short workspace, SPX_ENOTSUP for n >= 2^31; n == 0 or
+ * zero lines is SPX_OK with no launch.
+ * spx_sort_plan returns the number of radix passes the geometry takes (0: the
+ * LDS path; < 0 on bad arguments) and writes the longest LDS-path line and
+ * the radix tile length (either pointer may be NULL). */
+int64_t spx_sort_workspace(int dtype, int64_t outer, int64_t n, int64_t inner, int want_idx);
+int spx_sort(int dtype, const void* in, void* out_vals, int64_t* out_idx, int64_t outer, int64_t n,
+             int64_t inner, void* workspace, size_t workspace_bytes, void* stream);
+int spx_sort_plan(int dtype, int64_t outer, int64_t n, int64_t inner, int64_t* lds_max, int64_t* tile);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

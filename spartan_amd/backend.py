@@ -116,7 +116,12 @@ _SIGS = {
     'spx_scan': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                   ctypes.c_void_p], ctypes.c_int),
-    'spx_comm_load': ([ctypes.c_char_p], ctypes.c_int),
+    'spx_sort_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int],
+                           ctypes.c_int64),
+    'spx_sort': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    'spx_sort_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
+    'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
                       ctypes.c_int),
@@ -205,6 +210,22 @@ def scan_plan(outer, n, inner, dtype):
   if need < 0:
     raise ValueError('scan_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
   return ('chunked', SCAN_CHUNK) if need > 0 else ('line', int(n))
+
+
+SORT_LDS_MAX = 2048  # longest line spx_sort sorts in LDS (csrc/sort_kernels.h)
+SORT_TILE = 16384    # keys per workgroup and radix pass (csrc/sort_kernels.h)
+
+
+def sort_plan(outer, n, inner, dtype, want_idx=False):
+  """(path, passes) spx_sort uses for an (outer, n, inner) sort of ``dtype``:
+  ('lds', 0) -- lines of at most SORT_LDS_MAX keys, sorted in LDS, no
+  workspace -- or ('radix', passes), least-significant-digit passes over
+  tiles of SORT_TILE keys.  The library's own answer (spx_sort_plan);
+  ``want_idx`` changes the workspace, not the path."""
+  rc = load_library().spx_sort_plan(spx_dtype(dtype), int(outer), int(n), int(inner), None, None)
+  if rc < 0:
+    raise ValueError('sort_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
+  return ('radix', rc) if rc > 0 else ('lds', 0)
 
 
 def _arr(vals):
@@ -877,6 +898,40 @@ class HipBackend:
                              ctypes.c_void_p(totals.data_ptr() if totals is not None else 0),
                              1 if exclusive else 0, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
                              ws.numel() if ws is not None else 0, self.stream()), 'spx_scan')
+    if ev is not None:
+      ev[1].record()
+
+  # ----------------------------------------------------------------- sort
+  def sort(self, src, out_vals, out_idx, axis_geom):
+    """Stable ascending sort of the contiguous tensor ``src`` viewed as
+    (outer, n, inner) = ``axis_geom`` along n (spx_sort), in NumPy's order
+    (NaNs last, -0.0 == +0.0).  ``out_vals`` (src's dtype) receives the
+    sorted values, ``out_idx`` (int64) the positions within the line --
+    np.argsort(kind='stable'); either may be None, not both, and neither may
+    be ``src``.  Asynchronous on the current stream."""
+    outer, n, inner = (int(v) for v in axis_geom)
+    dt = np_dtype(src.dtype)
+    if not src.is_contiguous() or src.numel() != outer * n * inner:
+      raise ValueError('sort: src must be contiguous with %d elements' % (outer * n * inner))
+    if out_vals is None and out_idx is None:
+      raise ValueError('sort: out_vals and out_idx are both None')
+    for name, t, odt in (('out_vals', out_vals, dt), ('out_idx', out_idx, np.dtype(np.int64))):
+      if t is None:
+        continue
+      if np_dtype(t.dtype) != odt or not t.is_contiguous() or t.numel() != src.numel():
+        raise ValueError('sort: %s must be a contiguous %s tensor of src\'s size' % (name, odt))
+      if src.numel() and t.data_ptr() == src.data_ptr():
+        raise ValueError('sort: %s may not be src' % name)
+    need = self.lib.spx_sort_workspace(spx_dtype(dt), outer, n, inner, 1 if out_idx is not None else 0)
+    if need < 0:
+      raise ValueError('sort: bad geometry %s' % (axis_geom,))
+    if src.numel() == 0:
+      return
+    ws = self._workspace(int(need), src.device) if need > 0 else None
+    ev = self._aot_events('spx_sort')
+    _check(self.lib.spx_sort(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(out_vals), _ptr(out_idx),
+                             outer, n, inner, _ptr(ws), ws.numel() if ws is not None else 0, self.stream()),
+           'spx_sort')
     if ev is not None:
       ev[1].record()
 

@@ -15,6 +15,7 @@ from .reduce import reduce
 from .reshape import reshape
 from .scan import scan
 from .slice import slice_expr
+from .sort import argpartition, argsort, partition, sort
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write
 
