@@ -30,7 +30,8 @@ extern "C" {
 
 #define SPX_ABI_VERSION 3  /* 2: spx_kmeans_assign dist_dtype; collectives; 3: spx_kmeans_step */
 /* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan,
- * spx_sort_workspace, spx_sort, spx_sort_plan */
+ * spx_sort_workspace, spx_sort, spx_sort_plan, spx_take, spx_compact_workspace,
+ * spx_compact_count, spx_compact */
 
 /* error codes */
 #define SPX_OK 0
@@ -300,6 +301,49 @@ int64_t spx_sort_workspace(int dtype, int64_t outer, int64_t n, int64_t inner, i
 int spx_sort(int dtype, const void* in, void* out_vals, int64_t* out_idx, int64_t outer, int64_t n,
              int64_t inner, void* workspace, size_t workspace_bytes, void* stream);
 int spx_sort_plan(int dtype, int64_t outer, int64_t n, int64_t inner, int64_t* lds_max, int64_t* tile);
+
+/* ---------------------------------------------------------- take / compress
+ * Indexing a tile by an index array or a mask: np.take(a, idx, axis) -- the
+ * integer path of spartan/expr/filter.py:50-76 -- and np.compress / a[mask].
+ * Blocks are dense row-major, viewed as (outer, n, inner) as in spx_scan.
+ * Values move as bit patterns of their element size (1 / 4 / 8 bytes; `dtype`
+ * only selects the size); no atomics; the same input gives the same bits.
+ * Arguments are checked before any device work: SPX_EINVAL for null or
+ * negative arguments, an unknown dtype or a short workspace; empty work is
+ * SPX_OK with no launch.  Additive since ABI 3.
+ *
+ * spx_take: `src` is the block (outer, n_local, inner) holding rows [lo, lo +
+ * n_local) of an axis of length n_total; idx holds m indices (idx_dtype I32 /
+ * I64).  For j < m, r = idx[j] (+ n_total when negative):
+ *   r outside [0, n_total): *err = 1 (a device word the call clears first),
+ *     nothing is read or written for j;
+ *   r outside [lo, lo + n_local): out row j is left untouched;
+ *   otherwise out[o * out_outer_stride + j * out_row_stride + c] =
+ *     src[o, r - lo, c] (strides in elements, c < inner contiguous).
+ * The range test comes before any address is formed.  Rows shorter than 64
+ * units (a unit: 16 bytes where the row bytes, both strides and both pointers
+ * are multiples of 16, one element otherwise) take one lane per unit, longer
+ * rows a wave (from 2048 units a workgroup) per four rows.
+ *
+ * spx_compact_count / spx_compact: `mask` is n bytes, any nonzero byte selects.
+ * spx_compact_count counts the selected bytes per tile of a fixed number of
+ * mask bytes into an int64 table in the workspace, scans the table exclusively
+ * in place and writes the total to the DEVICE word `total` (n == 0: the word is
+cleared by a memset, no kernel is launched).  spx_compact reads
+ * the mask again, ranks the selected positions of a tile (wave ballots and
+ * popcounts, wave counts met in LDS) and writes out[o, base[tile] + rank, :] =
+ * in[o, j, :]; `out` is the dense block (outer, count, inner) and `count` must
+ * be the total (positions at or past `count` are not written).  `workspace` is
+ * the one spx_compact_count filled: spx_compact_workspace(n) bytes (0 for n ==
+ * 0, < 0 on a bad n), 8-byte aligned; its first 8 * ceil(n / tile) bytes are
+ * the table.  No launch has one workgroup wait for another. */
+int spx_take(int dtype, int idx_dtype, const void* src, const void* idx, void* out, int64_t outer,
+             int64_t n_total, int64_t lo, int64_t n_local, int64_t m, int64_t inner, int64_t out_outer_stride,
+             int64_t out_row_stride, int32_t* err, void* stream);
+int64_t spx_compact_workspace(int64_t n);
+int spx_compact_count(const void* mask, int64_t n, int64_t* total, void* workspace, size_t bytes, void* stream);
+int spx_compact(int dtype, const void* in, const void* mask, void* out, int64_t outer, int64_t n, int64_t inner,
+                int64_t count, const void* workspace, size_t bytes, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

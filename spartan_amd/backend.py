@@ -121,6 +121,15 @@ _SIGS = {
     'spx_sort': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
     'spx_sort_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
+    'spx_take': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    'spx_compact_workspace': ([ctypes.c_int64], ctypes.c_int64),
+    'spx_compact_count': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                           ctypes.c_void_p], ctypes.c_int),
+    'spx_compact': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+                    ctypes.c_int),
     'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -226,6 +235,29 @@ def sort_plan(outer, n, inner, dtype, want_idx=False):
   if rc < 0:
     raise ValueError('sort_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
   return ('radix', rc) if rc > 0 else ('lds', 0)
+
+
+def compact_tile():
+  """Mask bytes per workgroup of spx_compact_count / spx_compact
+  (COMPACT_TILE in csrc/index_kernels.h), read from the library: the
+  workspace starts with one int64 per tile, so the tile is the longest mask
+  whose workspace is a single entry.  Also ``backend.COMPACT_TILE``."""
+  ws = load_library().spx_compact_workspace
+  lo, hi = 1, 1 << 40  # ws(lo) == 8 < ws(hi)
+  while hi - lo > 1:
+    mid = (lo + hi) // 2
+    if ws(mid) <= 8:
+      lo = mid
+    else:
+      hi = mid
+  return lo
+
+
+def __getattr__(name):
+  if name == 'COMPACT_TILE':
+    globals()['COMPACT_TILE'] = t = compact_tile()
+    return t
+  raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
 def _arr(vals):
@@ -932,6 +964,105 @@ class HipBackend:
     _check(self.lib.spx_sort(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(out_vals), _ptr(out_idx),
                              outer, n, inner, _ptr(ws), ws.numel() if ws is not None else 0, self.stream()),
            'spx_sort')
+    if ev is not None:
+      ev[1].record()
+
+  # ------------------------------------------------------- take / compress
+  def take(self, src, idx, out, geom, lo, n_total, out_strides=None):
+    """out[o, j, :] = src[o, idx[j] - lo, :] (spx_take).  ``src`` is the
+    contiguous block ``geom`` = (outer, n_local, inner) holding rows [lo, lo +
+    n_local) of an axis of length ``n_total``; ``idx`` a contiguous 1-d int32 /
+    int64 tensor of m indices, negative ones wrapped by n_total.  ``out``
+    (src's dtype, contiguous) is addressed from its first element by
+    ``out_strides`` = (outer stride, row stride) in elements -- default the
+    dense (m * inner, inner) -- and rows whose index falls outside [lo, lo +
+    n_local) are left untouched.  An index outside [-n_total, n_total) raises
+    IndexError (the device flag is read back: the call waits for the
+    kernel); nothing is read or written for it."""
+    import torch
+    outer, n_local, inner = (int(v) for v in geom)
+    lo, n_total = int(lo), int(n_total)
+    dt = np_dtype(src.dtype)
+    if not src.is_contiguous() or src.numel() != outer * n_local * inner or min(outer, n_local, inner) < 0:
+      raise ValueError('take: src must be contiguous with %d elements' % (outer * n_local * inner))
+    if idx.dim() != 1 or not idx.is_contiguous() or np_dtype(idx.dtype) not in (np.dtype(np.int32), np.dtype(np.int64)):
+      raise ValueError('take: idx must be a contiguous 1-d int32 / int64 tensor')
+    if lo < 0 or n_total < 0 or lo + n_local > n_total:
+      raise ValueError('take: rows [%d, %d) are not inside an axis of length %d' % (lo, lo + n_local, n_total))
+    m = idx.numel()
+    oos, ors = (m * inner, inner) if out_strides is None else (int(v) for v in out_strides)
+    if out.dtype != src.dtype or not out.is_contiguous():
+      raise ValueError('take: out must be a contiguous %s tensor' % dt)
+    if outer == 0 or m == 0 or inner == 0:
+      return
+    if ors < inner or (outer > 1 and oos < inner) or (outer - 1) * oos + (m - 1) * ors + inner > out.numel():
+      raise ValueError('take: out of %d elements does not hold strides (%d, %d) of %d x %d rows of %d'
+                       % (out.numel(), oos, ors, outer, m, inner))
+    if out.data_ptr() == src.data_ptr() and src.numel():
+      raise ValueError('take: out may not be src')
+    err = torch.empty((1,), dtype=torch.int32, device=src.device)
+    ev = self._aot_events('spx_take')
+    _check(self.lib.spx_take(spx_dtype(dt), spx_dtype(np_dtype(idx.dtype)), _ptr(src), _ptr(idx), _ptr(out), outer,
+                             n_total, lo, n_local, m, inner, oos, ors, _ptr(err), self.stream()), 'spx_take')
+    if ev is not None:
+      ev[1].record()
+    if int(err.item()):
+      raise IndexError('take: an index is out of bounds for an axis of length %d' % n_total)
+
+  def compact_count(self, mask):
+    """(total, workspace) of the contiguous bool / uint8 tensor ``mask``
+    (spx_compact_count): the number of nonzero bytes, read back from the
+    device (the call waits), and the workspace with the scanned tile table
+    that ``compact`` with the same mask needs."""
+    import torch
+    if not mask.is_contiguous() or mask.element_size() != 1:
+      raise ValueError('compact_count: mask must be a contiguous bool / uint8 tensor')
+    n = mask.numel()
+    if n == 0:
+      return 0, None
+    need = int(self.lib.spx_compact_workspace(n))
+    if need < 0:
+      raise ValueError('compact_count: bad length %d' % n)
+    buf = torch.empty((need + 8,), dtype=torch.uint8, device=mask.device)  # the workspace and the total's word
+    ev = self._aot_events('spx_compact_count')
+    _check(self.lib.spx_compact_count(_ptr(mask), n, ctypes.c_void_p(buf.data_ptr() + need), _ptr(buf), need,
+                                      self.stream()), 'spx_compact_count')
+    if ev is not None:
+      ev[1].record()
+    return int(buf[need:].view(torch.int64).item()), buf[:need]
+
+  def compact(self, src, mask, out, geom, workspace):
+    """out[o, k, :] = src[o, j_k, :] for the k-th nonzero byte j_k of ``mask``
+    (spx_compact).  ``src`` is the contiguous block ``geom`` = (outer, n,
+    inner), ``mask`` the n bytes ``compact_count`` saw and ``workspace`` what
+    it returned; ``out`` is the dense (outer, total, inner) block of src's
+    dtype.  Asynchronous on the current stream."""
+    outer, n, inner = (int(v) for v in geom)
+    dt = np_dtype(src.dtype)
+    if not src.is_contiguous() or src.numel() != outer * n * inner or min(outer, n, inner) < 0:
+      raise ValueError('compact: src must be contiguous with %d elements' % (outer * n * inner))
+    if not mask.is_contiguous() or mask.element_size() != 1 or mask.numel() != n:
+      raise ValueError('compact: mask must be a contiguous bool / uint8 tensor of %d bytes' % n)
+    if out.dtype != src.dtype or not out.is_contiguous():
+      raise ValueError('compact: out must be a contiguous %s tensor' % dt)
+    lines = outer * inner
+    if lines == 0 or n == 0:
+      if out.numel():
+        raise ValueError('compact: out must be empty')
+      return
+    if out.numel() % lines or out.numel() // lines > n:
+      raise ValueError('compact: out of %d elements is not (outer, count, inner) with count <= %d' % (out.numel(), n))
+    count = out.numel() // lines
+    if count == 0:
+      return
+    need = int(self.lib.spx_compact_workspace(n))
+    if workspace is None or workspace.numel() < need or workspace.element_size() != 1:
+      raise ValueError('compact: the workspace of compact_count(mask) is needed (%d bytes)' % need)
+    if out.data_ptr() == src.data_ptr():
+      raise ValueError('compact: out may not be src')
+    ev = self._aot_events('spx_compact')
+    _check(self.lib.spx_compact(spx_dtype(dt), _ptr(src), _ptr(mask), _ptr(out), outer, n, inner, count,
+                                _ptr(workspace), workspace.numel(), self.stream()), 'spx_compact')
     if ev is not None:
       ev[1].record()
 

@@ -7,6 +7,7 @@ from .builtins import (abs, add, arange, argmax, argmin, astype, bincount, conca
                        ln, log, maximum, max, mean, min, minimum, multiply, ones, power, rand, randn,
                        size, sqrt, square, std, sub, sum, zeros)
 from .dot import dot
+from .filter import compress, take
 from .join import map2, outer
 from .map import map
 from .map_with_location import map_with_location, region_map

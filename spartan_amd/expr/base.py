@@ -208,8 +208,13 @@ class Expr:
     """Basic indexing (reference base.py:388-430): slices give a zero-copy
     slice view; an int index drops its dimension and ``newaxis`` inserts a
     unit dimension -- the reference's ReshapeExpr over the SliceExpr, here a
-    zero-copy UnitDims view."""
+    zero-copy UnitDims view.  An expression as the index (not inside a
+    tuple) is NumPy's integer-array / boolean indexing, lazily
+    (expr/filter.py); a raw host array or list is refused as before."""
     from .slice import slice_expr, unit_dims
+    if isinstance(idx, Expr):
+      from .filter import getitem
+      return getitem(self, idx)
     items = idx if isinstance(idx, tuple) else (idx,)
     if not any(_is_newaxis(i) or isinstance(i, (int, np.integer)) for i in items):
       return slice_expr(self, idx)
