@@ -31,7 +31,7 @@ extern "C" {
 #define SPX_ABI_VERSION 3  /* 2: spx_kmeans_assign dist_dtype; collectives; 3: spx_kmeans_step */
 /* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan,
  * spx_sort_workspace, spx_sort, spx_sort_plan, spx_take, spx_compact_workspace,
- * spx_compact_count, spx_compact */
+ * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool */
 
 /* error codes */
 #define SPX_OK 0
@@ -344,6 +344,35 @@ int64_t spx_compact_workspace(int64_t n);
 int spx_compact_count(const void* mask, int64_t n, int64_t* total, void* workspace, size_t bytes, void* stream);
 int spx_compact(int dtype, const void* in, const void* mask, void* out, int64_t outer, int64_t n, int64_t inner,
                 int64_t count, const void* workspace, size_t bytes, void* stream);
+
+/* ------------------------------------------------------ stencil / maxpool
+ * The convnet pair of spartan/expr/stencil.py on contiguous blocks.
+ * spx_stencil replaces _convolve (stencil.py:27-43), a Parakeet imap of the
+ * scalar loop: images (N, C, W, H), filters (F, C, fw, fh), out (N, F, W, H),
+ *   out[n, f, x, y] = sum over c, i, j with x + i < W and y + j < H of
+ *                     images[n, c, x + i, y + j] * filters[f, c, i, j]
+ * -- cross-correlation anchored at the top-left, taps past the bottom / right
+ * edge dropped.  Per image it is one MFMA product with M = F, N = W H, K = C fw
+ * fh whose B operand (the shifted, clipped image) is formed while staging into
+ * LDS and never written to memory; float32 and float64 only; one accumulation
+ * chain per element.  spx_stencil_plan returns the block tile (rows of F,
+ * columns of W H, K-tile) of a dtype; any of the three pointers may be NULL.
+ * spx_maxpool is the loop _maxpool has in its commented-out lines
+ * (stencil.py:58-67; the live body is a stub that returns a constant array):
+ * in (NC, W, H), out (NC, ceil(W / stride), ceil(H / stride)),
+ *   out[r, p, q] = max over i, j < pool with p stride + i < W and q stride + j < H
+ *                  of in[r, p stride + i, q stride + j]
+ * for the five dtypes (bool as bytes); every window holds its first element,
+ * so there is no fill value; NaN propagates as in np.maximum.  Both: N (NC)
+ * == 0 launches nothing; SPX_EINVAL for a bad dtype, a null pointer or a
+ * non-positive extent, SPX_ENOTSUP where an extent overflows the kernel's
+ * indices (stencil: (C + 16) W H, F W H, F C fw fh and (fw + 1) H must stay
+ * below 2^31).  No atomics; no workgroup waits for another. */
+int spx_stencil_plan(int dtype, int64_t* bm, int64_t* bn, int64_t* bk);
+int spx_stencil(int dtype, const void* images, const void* filters, void* out, int64_t N, int64_t C, int64_t W,
+                int64_t H, int64_t F, int64_t fw, int64_t fh, void* stream);
+int spx_maxpool(int dtype, const void* in, void* out, int64_t NC, int64_t W, int64_t H, int64_t pool,
+                int64_t stride, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

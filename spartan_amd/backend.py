@@ -130,6 +130,12 @@ _SIGS = {
     'spx_compact': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                      ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
                     ctypes.c_int),
+    'spx_stencil_plan': ([ctypes.c_int, _I64P, _I64P, _I64P], ctypes.c_int),
+    'spx_stencil': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
+                    ctypes.c_int),
+    'spx_maxpool': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -251,6 +257,18 @@ def compact_tile():
     else:
       hi = mid
   return lo
+
+
+def stencil_plan(dtype):
+  """(bm, bn, bk): the block tile of spx_stencil for ``dtype`` (float32 /
+  float64) -- rows of F, columns of W * H and the K-tile of C * fw * fh
+  (StencilTile in csrc/stencil_kernels.h), read from the library."""
+  dt = np.dtype(dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('stencil_plan: dtype %s has no stencil kernel (float32 / float64)' % dt)
+  v = [ctypes.c_int64(0) for _ in range(3)]
+  _check(load_library().spx_stencil_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_stencil_plan')
+  return tuple(int(x.value) for x in v)
 
 
 def __getattr__(name):
@@ -1063,6 +1081,74 @@ class HipBackend:
     ev = self._aot_events('spx_compact')
     _check(self.lib.spx_compact(spx_dtype(dt), _ptr(src), _ptr(mask), _ptr(out), outer, n, inner, count,
                                 _ptr(workspace), workspace.numel(), self.stream()), 'spx_compact')
+    if ev is not None:
+      ev[1].record()
+
+  # ------------------------------------------------------ stencil / maxpool
+  def stencil(self, images, filters, out):
+    """out[n, f, x, y] = sum over c, i, j with x + i < W, y + j < H of
+    images[n, c, x + i, y + j] * filters[f, c, i, j] (spx_stencil).  All three
+    are contiguous 4-d tensors of one dtype, float32 or float64: images (N, C,
+    W, H), filters (F, C, fw, fh), out (N, F, W, H).  Asynchronous on the
+    current stream."""
+    dt = np_dtype(images.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise TypeError('stencil: dtype %s has no stencil kernel (float32 / float64)' % dt)
+    if filters.dtype != images.dtype or out.dtype != images.dtype:
+      raise TypeError('stencil: images, filters and out must share one dtype (%s, %s, %s)'
+                      % (dt, np_dtype(filters.dtype), np_dtype(out.dtype)))
+    if images.dim() != 4 or filters.dim() != 4 or out.dim() != 4:
+      raise ValueError('stencil: images, filters and out must be 4-d')
+    N, C, W, H = (int(v) for v in images.shape)
+    F, fc, fw, fh = (int(v) for v in filters.shape)
+    if fc != C:
+      raise ValueError('stencil: images have %d channels, filters %d' % (C, fc))
+    if min(C, W, H, F, fw, fh) < 1:
+      raise ValueError('stencil: empty extent (images %s, filters %s)' % (tuple(images.shape), tuple(filters.shape)))
+    if tuple(out.shape) != (N, F, W, H):
+      raise ValueError('stencil: out must have shape %s, not %s' % ((N, F, W, H), tuple(out.shape)))
+    if not (images.is_contiguous() and filters.is_contiguous() and out.is_contiguous()):
+      raise ValueError('stencil: images, filters and out must be contiguous')
+    if N == 0:
+      return
+    if out.data_ptr() in (images.data_ptr(), filters.data_ptr()):
+      raise ValueError('stencil: out may not be an input')
+    ev = self._aot_events('spx_stencil')
+    _check(self.lib.spx_stencil(spx_dtype(dt), _ptr(images), _ptr(filters), _ptr(out), N, C, W, H, F, fw, fh,
+                                self.stream()), 'spx_stencil')
+    if ev is not None:
+      ev[1].record()
+
+  def maxpool(self, src, out, pool_size, stride):
+    """out[n, c, p, q] = max over i, j < pool_size with p stride + i < W and
+    q stride + j < H of src[n, c, p stride + i, q stride + j] (spx_maxpool).
+    ``src`` is a contiguous (N, C, W, H) tensor of any of the five dtypes,
+    ``out`` the contiguous (N, C, ceil(W / stride), ceil(H / stride)) tensor
+    of the same dtype.  NaN propagates as in np.maximum.  Asynchronous on the
+    current stream."""
+    pool_size, stride = int(pool_size), int(stride)
+    if pool_size < 1 or stride < 1:
+      raise ValueError('maxpool: pool_size %d and stride %d must be at least 1' % (pool_size, stride))
+    dt = np_dtype(src.dtype)
+    if out.dtype != src.dtype:
+      raise TypeError('maxpool: out must have src\'s dtype %s' % dt)
+    if src.dim() != 4 or out.dim() != 4:
+      raise ValueError('maxpool: src and out must be 4-d')
+    N, C, W, H = (int(v) for v in src.shape)
+    if min(C, W, H) < 1:
+      raise ValueError('maxpool: empty extent %s' % (tuple(src.shape),))
+    want = (N, C, -(-W // stride), -(-H // stride))
+    if tuple(out.shape) != want:
+      raise ValueError('maxpool: out must have shape %s, not %s' % (want, tuple(out.shape)))
+    if not (src.is_contiguous() and out.is_contiguous()):
+      raise ValueError('maxpool: src and out must be contiguous')
+    if N == 0:
+      return
+    if out.data_ptr() == src.data_ptr():
+      raise ValueError('maxpool: out may not be src')
+    ev = self._aot_events('spx_maxpool')
+    _check(self.lib.spx_maxpool(spx_dtype(dt), _ptr(src), _ptr(out), N * C, W, H, pool_size, stride, self.stream()),
+           'spx_maxpool')
     if ev is not None:
       ev[1].record()
 

@@ -3,7 +3,7 @@
 // This file holds the ahead-of-time kernels (fills, reduction finalize, tile
 // merge, region copy, MFMA GEMM dispatch, arg-reduction combine), includes the
 // k-means, scan, sort and index families (kmeans_kernels.h, scan_kernels.h,
-// sort_kernels.h, index_kernels.h) and the module/launch
+// sort_kernels.h, index_kernels.h, stencil_kernels.h) and the module/launch
 // plumbing for the fused map / map+reduce kernels that spartan_amd/codegen.py
 // generates per expression.  Reference call sites replaced are cited per
 // entry point in include/spx.h.
@@ -771,6 +771,9 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
 
 // ========================================================= take / compress
 #include "index_kernels.h"
+
+// ===================================================== stencil / maxpool
+#include "stencil_kernels.h"
 
 // ============================================================ JIT modules
 extern "C" int spx_module_load(const void* image, size_t nbytes, void** module_out) {

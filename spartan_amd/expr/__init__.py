@@ -19,6 +19,7 @@ from .slice import slice_expr
 from .sort import argpartition, argsort, partition, sort
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write
+from . import stencil  # the submodule, as in the reference: stencil.stencil / stencil.maxpool
 
 Expr.outer = outer
 Expr.sum = sum
