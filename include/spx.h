@@ -31,7 +31,8 @@ extern "C" {
 #define SPX_ABI_VERSION 3  /* 2: spx_kmeans_assign dist_dtype; collectives; 3: spx_kmeans_step */
 /* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan,
  * spx_sort_workspace, spx_sort, spx_sort_plan, spx_take, spx_compact_workspace,
- * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool */
+ * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool,
+ * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan */
 
 /* error codes */
 #define SPX_OK 0
@@ -301,6 +302,76 @@ int64_t spx_sort_workspace(int dtype, int64_t outer, int64_t n, int64_t inner, i
 int spx_sort(int dtype, const void* in, void* out_vals, int64_t* out_idx, int64_t outer, int64_t n,
              int64_t inner, void* workspace, size_t workspace_bytes, void* stream);
 int spx_sort_plan(int dtype, int64_t outer, int64_t n, int64_t inner, int64_t* lds_max, int64_t* tile);
+
+/* ------------------------------------------------------------ topk / argtopk
+ * The first k elements of each line's stable order, without sorting the line.
+ * `in` is a dense row-major block viewed as (outer, n, inner) as in spx_sort;
+ * the outputs are dense (outer, k, inner).  Additive since ABI 3.
+ *   largest == 0: positions np.argsort(x, kind='stable')[:k] -- spx_sort's
+ *     order (integers signed, bool 0 < 1, -0.0 == +0.0, NaNs tie and come after
+ *     +inf), equal keys lower position first;
+ *   largest != 0: descending by value, equal keys lower position first, NaNs
+ *     still last: np.argsort(-x, kind='stable')[:k] for floats and
+ *     np.argsort(~x, kind='stable')[:k] for BOOL / I32 / I64;
+ *   out_vals  NULL, or in's dtype: the selected elements' bit patterns;
+ *   out_idx   NULL, or int64: the positions within the line, or, with in_idx
+ *             (int64, in's shape; may be NULL), in_idx at those positions --
+ *             ties are still broken by position.  Both outputs NULL: SPX_EINVAL.
+ * 1 <= k <= n, k at most the limit the plan call reports through kmax (2048:
+ * the selected candidates of a line are ordered by one LDS sort); a larger k is
+ * SPX_ENOTSUP, as is n >= 2^31.  Lines of n <= 2048 are sorted in LDS and only
+ * the first k stored (no workspace).  Longer lines take a most-significant-
+ * digit radix select of 8 bits a pass over the order keys (three launches a
+ * pass: per-chunk digit counts of the keys matching the prefix, one workgroup
+ * per line picks the digit of the k-th key, one wave per chunk counts the keys
+ * now known to precede it), one stable compaction
+ * pass that writes the k candidates in position order and one LDS sort of the
+ * candidates: the line is read (key bytes + 1) times and never written, and
+ * strided lines (inner > 1) are indexed with their stride.  No launch has one
+ * workgroup wait for another; no float atomics; the same input and geometry
+ * give the same bits.  workspace_bytes must be at least the workspace call's
+ * answer for (dtype, outer, n, inner, k, out_idx != NULL) (0 for the LDS path;
+ * < 0 on bad arguments).  Arguments are checked before any device work:
+ * SPX_EINVAL for null / negative arguments, an unknown dtype, k < 1, k > n or a
+ * short workspace; zero lines is SPX_OK with no launch.  The plan call returns
+ * the number of select passes (0: the LDS path; < 0 on bad arguments) and
+ * writes the k limit and the chunk of a line one workgroup counts (either
+ * pointer may be NULL). */
+int64_t spx_topk_workspace(int dtype, int64_t outer, int64_t n, int64_t inner, int64_t k, int want_idx);
+int spx_topk(int dtype, const void* in, const int64_t* in_idx, void* out_vals, int64_t* out_idx, int64_t outer,
+             int64_t n, int64_t inner, int64_t k, int largest, void* workspace, size_t workspace_bytes,
+             void* stream);
+int spx_topk_plan(int dtype, int64_t outer, int64_t n, int64_t inner, int64_t k, int64_t* kmax, int64_t* chunk);
+
+/* -------------------------------------------------------- nearest neighbours
+ * The brute-force search of NearestNeighbors.kneighbors
+ * (spartan/examples/sklearn/neighbors/unsupervised.py), fused: distances and
+ * selection in one kernel, the (Q, N) matrix never written.  points F32 / F64
+ * (N, D) with row stride ldp; queries fp64, dense (Q, D).  s[i, j] is the fp64
+ * sum over d = 0..D-1, in that order, of (queries[i, d] - (double)points[j,
+ * d])^2, every difference, square and add rounded separately and the
+ * accumulator starting at +0.0: the value whose sqrt the distance-matrix call
+ * above stores.  The neighbours of query i are the first k of the order (s[i,
+ * j], j) ascending, NaN sums after +inf.  out_s (Q, k) fp64 receives the sums
+ * (not their roots; NaNs canonical), out_idx (Q, k) int64 index_base + j.
+ * 1 <= k <= N, k at most the limit the plan call reports through kmax (128); a
+ * larger k is SPX_ENOTSUP, as is N >= 2^31; any D >= 1.  The points are cut
+ * into ranges over the grid's second dimension so that a few queries still
+ * fill the GPU; each (64-query tile, range) leaves its k best in the workspace
+ * and the selection kernels above pick per query among the ranges' lists.  The
+ * composite (s, j) is a total order, so the result does not depend on the
+ * ranges or on the order in which candidates met.  No workgroup waits for
+ * another; no float atomics; same input, same bits.  workspace_bytes must be at
+ * least the workspace call's answer (< 0 on bad arguments); SPX_EINVAL for null
+ * pointers, negative sizes, ldp < D, k < 1, k > N or a short workspace, checked
+ * before any device work; Q == 0 is SPX_OK with no launch.  The plan call
+ * returns the number of point ranges (< 0 on bad arguments) and writes the k
+ * limit and the range length (either pointer may be NULL). */
+int64_t spx_knn_workspace(int dtype, int64_t Q, int64_t N, int64_t D, int64_t k);
+int spx_knn(int dtype, int64_t Q, int64_t N, int64_t D, int64_t k, const void* points, int64_t ldp,
+            const double* queries, int64_t index_base, double* out_s, int64_t* out_idx, void* workspace,
+            size_t workspace_bytes, void* stream);
+int spx_knn_plan(int dtype, int64_t Q, int64_t N, int64_t D, int64_t k, int64_t* kmax, int64_t* chunk);
 
 /* ---------------------------------------------------------- take / compress
  * Indexing a tile by an index array or a mask: np.take(a, idx, axis) -- the

@@ -121,6 +121,20 @@ _SIGS = {
     'spx_sort': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
     'spx_sort_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
+    'spx_topk_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                            ctypes.c_int], ctypes.c_int64),
+    'spx_topk': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                  ctypes.c_void_p], ctypes.c_int),
+    'spx_topk_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P],
+                      ctypes.c_int),
+    'spx_knn_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64],
+                          ctypes.c_int64),
+    'spx_knn': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                 ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    'spx_knn_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P],
+                     ctypes.c_int),
     'spx_take': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
@@ -243,6 +257,42 @@ def sort_plan(outer, n, inner, dtype, want_idx=False):
   return ('radix', rc) if rc > 0 else ('lds', 0)
 
 
+def topk_plan(outer, n, inner, dtype, k=1):
+  """(path, passes, chunk) spx_topk uses for an (outer, n, inner) selection
+  of ``dtype``: ('lds', 0, chunk) -- lines of at most SORT_LDS_MAX elements,
+  sorted in LDS -- or ('select', passes, chunk), most-significant-digit radix
+  select passes over chunks of ``chunk`` elements (spx_topk_plan)."""
+  chunk = ctypes.c_int64(0)
+  rc = load_library().spx_topk_plan(spx_dtype(dtype), int(outer), int(n), int(inner), int(k), None,
+                                    ctypes.byref(chunk))
+  if rc < 0:
+    raise ValueError('topk_plan: bad geometry (%s, %s, %s), k %s' % (outer, n, inner, k))
+  return ('select', rc, int(chunk.value)) if rc > 0 else ('lds', 0, int(chunk.value))
+
+
+def knn_plan(Q, N, D, k, dtype=np.float32):
+  """(number of point ranges, range length) of spx_knn (spx_knn_plan)."""
+  chunk = ctypes.c_int64(0)
+  rc = load_library().spx_knn_plan(spx_dtype(dtype), int(Q), int(N), int(D), int(k), None, ctypes.byref(chunk))
+  if rc < 0:
+    raise ValueError('knn_plan: bad arguments (Q %s, N %s, D %s, k %s)' % (Q, N, D, k))
+  return rc, int(chunk.value)
+
+
+def _k_limit(which):
+  """TOPK_K_MAX / KNN_K_MAX: the library's own limits, through the plan calls."""
+  if which in globals():
+    return globals()[which]
+  kmax = ctypes.c_int64(0)
+  lib = load_library()
+  if which == 'TOPK_K_MAX':
+    lib.spx_topk_plan(SPX_F32, 1, 1, 1, 1, ctypes.byref(kmax), None)
+  else:
+    lib.spx_knn_plan(SPX_F32, 1, 1, 1, 1, ctypes.byref(kmax), None)
+  globals()[which] = int(kmax.value)
+  return int(kmax.value)
+
+
 def compact_tile():
   """Mask bytes per workgroup of spx_compact_count / spx_compact
   (COMPACT_TILE in csrc/index_kernels.h), read from the library: the
@@ -275,6 +325,8 @@ def __getattr__(name):
   if name == 'COMPACT_TILE':
     globals()['COMPACT_TILE'] = t = compact_tile()
     return t
+  if name in ('TOPK_K_MAX', 'KNN_K_MAX'):
+    return _k_limit(name)
   raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
@@ -982,6 +1034,91 @@ class HipBackend:
     _check(self.lib.spx_sort(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(out_vals), _ptr(out_idx),
                              outer, n, inner, _ptr(ws), ws.numel() if ws is not None else 0, self.stream()),
            'spx_sort')
+    if ev is not None:
+      ev[1].record()
+
+  # ----------------------------------------------------------------- topk
+  def topk(self, src, in_idx, out_vals, out_idx, axis_geom, k, largest=False):
+    """The first ``k`` of each line's stable order (spx_topk): ``src`` is a
+    contiguous tensor viewed as (outer, n, inner) = ``axis_geom``; the outputs
+    are contiguous with outer * k * inner elements.  ``largest``: descending,
+    equal keys lower position first, NaNs still last.  ``out_vals`` (src's
+    dtype) receives the selected values, ``out_idx`` (int64) their positions
+    in the line or, with ``in_idx`` (int64, src's size), in_idx there; either
+    output may be None, not both.  Asynchronous on the current stream."""
+    outer, n, inner = (int(v) for v in axis_geom)
+    k = int(k)
+    dt = np_dtype(src.dtype)
+    i64 = np.dtype(np.int64)
+    if not src.is_contiguous() or src.numel() != outer * n * inner:
+      raise ValueError('topk: src must be contiguous with %d elements' % (outer * n * inner))
+    if out_vals is None and out_idx is None:
+      raise ValueError('topk: out_vals and out_idx are both None')
+    if k < 1 or (outer * inner > 0 and k > n):
+      raise ValueError('topk: k %d is outside [1, %d]' % (k, n))
+    if k > _k_limit('TOPK_K_MAX'):
+      raise ValueError('topk: k %d exceeds TOPK_K_MAX = %d' % (k, _k_limit('TOPK_K_MAX')))
+    if in_idx is not None and (np_dtype(in_idx.dtype) != i64 or not in_idx.is_contiguous()
+                               or in_idx.numel() != src.numel()):
+      raise ValueError('topk: in_idx must be a contiguous int64 tensor of src\'s size')
+    for name, t, odt in (('out_vals', out_vals, dt), ('out_idx', out_idx, i64)):
+      if t is None:
+        continue
+      if np_dtype(t.dtype) != odt or not t.is_contiguous() or t.numel() != outer * k * inner:
+        raise ValueError('topk: %s must be a contiguous %s tensor of %d elements' % (name, odt, outer * k * inner))
+      if src.numel() and t.data_ptr() == src.data_ptr():
+        raise ValueError('topk: %s may not be src' % name)
+    need = self.lib.spx_topk_workspace(spx_dtype(dt), outer, n, inner, k, 1 if out_idx is not None else 0)
+    if need < 0:
+      raise ValueError('topk: bad geometry %s, k %d' % (axis_geom, k))
+    if outer * inner == 0:
+      return
+    ws = self._workspace(int(need), src.device) if need > 0 else None
+    ev = self._aot_events('spx_topk')
+    _check(self.lib.spx_topk(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(in_idx), _ptr(out_vals),
+                             _ptr(out_idx), outer, n, inner, k, 1 if largest else 0, _ptr(ws),
+                             ws.numel() if ws is not None else 0, self.stream()), 'spx_topk')
+    if ev is not None:
+      ev[1].record()
+
+  def knn(self, points, queries, k, index_base, out_s, out_idx):
+    """The k nearest of ``points`` (N, D) float32 / float64, unit column
+    stride, to each row of ``queries`` (Q, D) float64 contiguous (spx_knn):
+    ``out_s`` (Q, k) float64 receives the exact-order sums of squared
+    differences, ascending by (sum, index), ``out_idx`` (Q, k) int64
+    index_base + the point's row.  Asynchronous on the current stream."""
+    k = int(k)
+    if points.dim() != 2 or queries.dim() != 2 or points.shape[1] != queries.shape[1]:
+      raise ValueError('knn: points (N, D) and queries (Q, D) expected, got %s and %s'
+                       % (tuple(points.shape), tuple(queries.shape)))
+    N, D = (int(v) for v in points.shape)
+    Q = int(queries.shape[0])
+    dt = np_dtype(points.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('knn: points must be float32 / float64, not %s' % dt)
+    if queries.dtype != self._f64() or not queries.is_contiguous():
+      raise ValueError('knn: queries must be a contiguous float64 tensor')
+    if D < 1 or (N > 1 and points.stride(1) != 1) or (N > 1 and points.stride(0) < D):
+      raise ValueError('knn: points need unit column stride and a row stride of at least D')
+    if k < 1 or k > N:
+      raise ValueError('knn: k %d is outside [1, N = %d]' % (k, N))
+    if k > _k_limit('KNN_K_MAX'):
+      raise ValueError('knn: k %d exceeds KNN_K_MAX = %d' % (k, _k_limit('KNN_K_MAX')))
+    for name, t, odt in (('out_s', out_s, np.dtype(np.float64)), ('out_idx', out_idx, np.dtype(np.int64))):
+      if np_dtype(t.dtype) != odt or not t.is_contiguous() or tuple(t.shape) != (Q, k):
+        raise ValueError('knn: %s must be a contiguous (%d, %d) %s tensor' % (name, Q, k, odt))
+    need = self.lib.spx_knn_workspace(spx_dtype(dt), Q, N, D, k)
+    if need < 0:
+      raise ValueError('knn: bad arguments (Q %d, N %d, D %d, k %d)' % (Q, N, D, k))
+    if Q == 0:
+      return
+    ldp = int(points.stride(0)) if N > 1 else D
+    ws = self._workspace(max(int(need), 8), points.device)
+    ev = self._aot_events('spx_knn')
+    _check(self.lib.spx_knn(spx_dtype(dt), Q, N, D, k, ctypes.c_void_p(points.data_ptr()), ldp,
+                            ctypes.c_void_p(queries.data_ptr()), int(index_base), ctypes.c_void_p(out_s.data_ptr()),
+                            ctypes.c_void_p(out_idx.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                            self.stream()), 'spx_knn')
     if ev is not None:
       ev[1].record()
 

@@ -769,6 +769,9 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
 // ========================================================= sort / argsort
 #include "sort_kernels.h"
 
+// ================================================= topk / nearest neighbours
+#include "topk_kernels.h"
+
 // ========================================================= take / compress
 #include "index_kernels.h"
 

@@ -17,6 +17,7 @@ from .reshape import reshape
 from .scan import scan
 from .slice import slice_expr
 from .sort import argpartition, argsort, partition, sort
+from .topk import argtopk, topk
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write
 from . import stencil  # the submodule, as in the reference: stencil.stencil / stencil.maxpool
