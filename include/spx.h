@@ -32,7 +32,8 @@ extern "C" {
 /* additive since 3 (no existing signature changed): spx_scan_workspace, spx_scan,
  * spx_sort_workspace, spx_sort, spx_sort_plan, spx_take, spx_compact_workspace,
  * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool,
- * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan */
+ * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
+ * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk */
 
 /* error codes */
 #define SPX_OK 0
@@ -444,6 +445,56 @@ int spx_stencil(int dtype, const void* images, const void* filters, void* out, i
                 int64_t H, int64_t F, int64_t fw, int64_t fh, void* stream);
 int spx_maxpool(int dtype, const void* in, void* out, int64_t NC, int64_t W, int64_t H, int64_t pool,
                 int64_t stride, void* stream);
+
+/* ------------------------------------------------- cholesky / triangular solve
+ * Dense linear algebra on one tile: the three mappers of
+ * spartan/examples/cholesky.py (scipy's dpotrf, dtrtrs / dtrsm, dsyrk / dgemm).
+ * float32 and float64 only (another dtype: SPX_ENOTSUP); row-major with leading
+ * dimensions in elements; asynchronous on the stream.  Arguments are checked
+ * before any device work: SPX_EINVAL for a null pointer, a negative size, a
+ * leading dimension below the row length or a short workspace, SPX_ENOTSUP for
+ * an extent whose tile count reaches 2^31; empty work is SPX_OK with no launch.
+ * No workgroup waits for another, no float atomics, the same input and
+ * geometry give the same bits.  Additive since ABI 3.
+ *
+ * The factorization: L = the lower Cholesky factor of the n x n matrix A.  Only
+ * A's lower triangle (i >= j) is read; L's strict upper triangle is written as
+ * +0.0; L may be A (then lda == ldl).  Blocked right-looking at two levels
+ * (the plan call reports the diagonal block nb, factored by one workgroup in
+ * LDS, and the outer panel nb_outer, the K of the trailing update).  `info` is a
+ * device int32 word the call clears first: it stays 0 on success and otherwise
+ * receives the 1-based order of the first leading minor whose pivot is <= 0 or
+ * NaN (LAPACK's info); the host never reads it inside the call, every launch
+ * still completes after a failed pivot and the rest of L is then unspecified.
+ * The workspace call's answer (0 here: the work is done in place on L; < 0 on
+ * bad arguments) is the least workspace_bytes.
+ *
+ * The triangular solve, in place on B (m x n), with a lower-triangular,
+ * non-unit L: side LEFT solves op(L) X = B (L m x m), side RIGHT X op(L) = B
+ * (L n x n); op N or T.  RIGHT/T and RIGHT/N have kernels of their own
+ * (diagonal blocks by substitution with true divisions -- no inverse, no
+ * reciprocal --, off-diagonal blocks on MFMA); the LEFT forms run them on a
+ * transposed copy of B in the workspace (m n elements).  No singularity check:
+ * a zero diagonal gives IEEE inf / NaN.
+ *
+ * The update: C[M,N] -= A[M,K] B[N,K]^T on v_mfma_f32_32x32x2_f32 /
+ * v_mfma_f64_16x16x4_f64, both operands read along their rows, one
+ * accumulation chain per element, C read and written once.  lower != 0 (needs
+ * M == N, C's diagonal on the tile diagonal): tiles strictly above the
+ * diagonal are not launched and diagonal tiles touch only i >= j. */
+#define SPX_SIDE_LEFT 0
+#define SPX_SIDE_RIGHT 1
+#define SPX_TRANS_N 0
+#define SPX_TRANS_T 1
+int spx_potrf_plan(int dtype, int64_t* nb, int64_t* nb_outer);
+int64_t spx_potrf_workspace(int dtype, int64_t n);
+int spx_potrf(int dtype, int64_t n, const void* A, int64_t lda, void* L, int64_t ldl, int32_t* info,
+              void* workspace, size_t workspace_bytes, void* stream);
+int64_t spx_trsm_workspace(int dtype, int side, int64_t m, int64_t n);
+int spx_trsm(int dtype, int side, int op, int64_t m, int64_t n, const void* L, int64_t ldl, void* B, int64_t ldb,
+             void* workspace, size_t workspace_bytes, void* stream);
+int spx_syrk(int dtype, int lower, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+             int64_t ldb, void* C, int64_t ldc, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

@@ -150,6 +150,17 @@ _SIGS = {
                     ctypes.c_int),
     'spx_maxpool': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                      ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
+    'spx_potrf_plan': ([ctypes.c_int, _I64P, _I64P], ctypes.c_int),
+    'spx_potrf_workspace': ([ctypes.c_int, ctypes.c_int64], ctypes.c_int64),
+    'spx_potrf': ([ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    'spx_trsm_workspace': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
+    'spx_trsm': ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+                 ctypes.c_int),
+    'spx_syrk': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
+                 ctypes.c_int),
     'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -318,6 +329,17 @@ def stencil_plan(dtype):
     raise TypeError('stencil_plan: dtype %s has no stencil kernel (float32 / float64)' % dt)
   v = [ctypes.c_int64(0) for _ in range(3)]
   _check(load_library().spx_stencil_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_stencil_plan')
+  return tuple(int(x.value) for x in v)
+
+
+def potrf_plan(dtype):
+  """(nb, nb_outer): the diagonal block one workgroup factors in LDS and the
+  outer panel (the K of the trailing update) of spx_potrf, from the library."""
+  dt = np.dtype(dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('potrf_plan: dtype %s has no Cholesky kernel (float32 / float64)' % dt)
+  v = [ctypes.c_int64(0) for _ in range(2)]
+  _check(load_library().spx_potrf_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_potrf_plan')
   return tuple(int(x.value) for x in v)
 
 
@@ -1286,6 +1308,96 @@ class HipBackend:
     ev = self._aot_events('spx_maxpool')
     _check(self.lib.spx_maxpool(spx_dtype(dt), _ptr(src), _ptr(out), N * C, W, H, pool_size, stride, self.stream()),
            'spx_maxpool')
+    if ev is not None:
+      ev[1].record()
+
+  # --------------------------------------------- cholesky / triangular solve
+  @staticmethod
+  def _matrix(name, t, rows=None, cols=None, dtype=None):
+    """(rows, cols, leading dimension) of a 2-d float32 / float64 tensor with
+    unit column stride and a row stride of at least its row length."""
+    if t.dim() != 2:
+      raise ValueError('%s must be 2-d, got shape %s' % (name, tuple(t.shape)))
+    dt = np_dtype(t.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('%s must be float32 / float64, not %s' % (name, dt))
+    if dtype is not None and dt != dtype:
+      raise ValueError('%s has dtype %s, expected %s' % (name, dt, dtype))
+    r, c = (int(v) for v in t.shape)
+    if (rows is not None and r != rows) or (cols is not None and c != cols):
+      raise ValueError('%s has shape %s, expected (%s, %s)' % (name, (r, c), rows, cols))
+    if (c > 1 and t.stride(1) != 1) or (r > 1 and t.stride(0) < c):
+      raise ValueError('%s needs unit column stride and a row stride of at least %d' % (name, c))
+    return r, c, (int(t.stride(0)) if r > 1 else max(c, 1))
+
+  def potrf(self, A, L):
+    """``L`` = the lower Cholesky factor of the square ``A`` (spx_potrf): only
+    A's lower triangle is read, L's strict upper triangle becomes +0.0, ``L``
+    may be ``A``.  Returns the one-element int32 device tensor ``info`` (0, or
+    the order of the first leading minor that is not positive definite);
+    nothing here reads it.  Asynchronous on the current stream."""
+    import torch
+    n, c, lda = self._matrix('potrf: A', A)
+    if n != c:
+      raise ValueError('potrf: A must be square, got %s' % ((n, c),))
+    dt = np_dtype(A.dtype)
+    _, _, ldl = self._matrix('potrf: L', L, n, n, dt)
+    if n and L.data_ptr() == A.data_ptr() and lda != ldl:
+      raise ValueError('potrf: in place needs the same row stride')
+    info = torch.zeros((1,), dtype=torch.int32, device=A.device)
+    need = self.lib.spx_potrf_workspace(spx_dtype(dt), n)
+    if need < 0:
+      raise ValueError('potrf: bad size %d' % n)
+    if n == 0:
+      return info
+    ws = self._workspace(int(need), A.device) if need > 0 else None
+    ev = self._aot_events('spx_potrf')
+    _check(self.lib.spx_potrf(spx_dtype(dt), n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(L.data_ptr()),
+                              ldl, ctypes.c_void_p(info.data_ptr()), _ptr(ws), ws.numel() if ws is not None else 0,
+                              self.stream()), 'spx_potrf')
+    if ev is not None:
+      ev[1].record()
+    return info
+
+  def trsm(self, L, B, side='L', trans=False):
+    """Solve with the lower-triangular, non-unit ``L`` in place on ``B`` (m, n)
+    (spx_trsm): side 'L' op(L) X = B with L (m, m), side 'R' X op(L) = B with
+    L (n, n); ``trans`` selects op = transpose.  Asynchronous."""
+    if side not in ('L', 'R'):
+      raise ValueError("trsm: side must be 'L' or 'R', not %r" % (side,))
+    m, n, ldb = self._matrix('trsm: B', B)
+    dt = np_dtype(B.dtype)
+    nl = m if side == 'L' else n
+    _, _, ldl = self._matrix('trsm: L', L, nl, nl, dt)
+    sd = 0 if side == 'L' else 1
+    need = self.lib.spx_trsm_workspace(spx_dtype(dt), sd, m, n)
+    if need < 0:
+      raise ValueError('trsm: bad sizes (%d, %d)' % (m, n))
+    if m == 0 or n == 0:
+      return
+    ws = self._workspace(int(need), B.device) if need > 0 else None
+    ev = self._aot_events('spx_trsm')
+    _check(self.lib.spx_trsm(spx_dtype(dt), sd, 1 if trans else 0, m, n, ctypes.c_void_p(L.data_ptr()), ldl,
+                             ctypes.c_void_p(B.data_ptr()), ldb, _ptr(ws), ws.numel() if ws is not None else 0,
+                             self.stream()), 'spx_trsm')
+    if ev is not None:
+      ev[1].record()
+
+  def syrk(self, A, B, C, lower=False):
+    """``C`` (M, N) -= ``A`` (M, K) @ ``B`` (N, K)^T (spx_syrk).  ``lower``
+    (M == N): only C's lower triangle is read and written.  Asynchronous."""
+    M, K, lda = self._matrix('syrk: A', A)
+    dt = np_dtype(A.dtype)
+    N, _, ldb = self._matrix('syrk: B', B, None, K, dt)
+    _, _, ldc = self._matrix('syrk: C', C, M, N, dt)
+    if lower and M != N:
+      raise ValueError('syrk: lower needs a square C, got (%d, %d)' % (M, N))
+    if M == 0 or N == 0 or K == 0:
+      return
+    ev = self._aot_events('spx_syrk')
+    _check(self.lib.spx_syrk(spx_dtype(dt), 1 if lower else 0, M, N, K, ctypes.c_void_p(A.data_ptr()), lda,
+                             ctypes.c_void_p(B.data_ptr()), ldb, ctypes.c_void_p(C.data_ptr()), ldc, self.stream()),
+           'spx_syrk')
     if ev is not None:
       ev[1].record()
 
