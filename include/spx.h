@@ -33,7 +33,8 @@ extern "C" {
  * spx_sort_workspace, spx_sort, spx_sort_plan, spx_take, spx_compact_workspace,
  * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool,
  * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
- * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk */
+ * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
+ * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr */
 
 /* error codes */
 #define SPX_OK 0
@@ -495,6 +496,47 @@ int spx_trsm(int dtype, int side, int op, int64_t m, int64_t n, const void* L, i
              void* workspace, size_t workspace_bytes, void* stream);
 int spx_syrk(int dtype, int lower, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
              int64_t ldb, void* C, int64_t ldc, void* stream);
+
+/* ------------------------------------------------------------- qr (TSQR)
+ * The reduced QR factorization A = Q R of a tall or square m x n matrix
+ * (m >= n) by communication-avoiding Householder QR: the thin QR that
+ * spartan/examples/ssvd/qr.py obtains from a Cholesky factor of A^T A, here
+ * backward stable for any conditioning and any rank.  float32 and float64 only
+ * (another dtype: SPX_ENOTSUP); row-major with leading dimensions in elements;
+ * asynchronous on the stream.
+ *
+ * The plan call returns SPX_OK and writes the column limit *nmax of the dtype
+ * (128 for float32, 64 for float64) and *rows = r(dtype, n), the rows one
+ * workgroup factors in LDS (a multiple of 64, at least 2 n; 0 where n > nmax);
+ * either pointer may be NULL.  The workspace call answers the bytes spx_geqr
+ * needs for (m, n) -- it grows monotonically in m and is about m n elements --
+ * or < 0 on bad arguments (m < n and n > nmax included).
+ *
+ * spx_geqr reads A once and never writes it: ceil(m / r) workgroups factor one
+ * block of r rows each, their n x n triangles are stacked and factored by the
+ * same kernel, and so on until one block remains.  R (n x n) receives that
+ * block's triangle with +0.0 strictly below the diagonal and its rows scaled so
+ * that diag(R) >= 0; the workspace receives every block's reflectors and taus
+ * and the sign matrix D.  spx_orgqr forms Q (m x n) = Q_0 D C from them, C the
+ * n x n seed (NULL: the identity; C is read only), so that A = Q R for C = I;
+ * it uses the workspace's stack regions as scratch for the tree's inner levels
+ * (which is why the workspace is not const) and leaves the reflectors intact:
+ * it may be called again with another seed.  Bytes beyond column n of any row
+ * of A, R, C and Q are neither read nor written.  A zero column below the
+ * diagonal gives tau = 0; column norms are accumulated in double (float data)
+ * or scaled by a power of two (double data).  No atomics, no workgroup waits
+ * for another, the same input and geometry give the same bits.
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a null pointer,
+ * a negative size, m < n, a leading dimension below n or a short workspace,
+ * SPX_ENOTSUP for n > nmax; m == 0 or n == 0 is SPX_OK with no launch.
+ * Additive since ABI 3. */
+int spx_geqr_plan(int dtype, int64_t n, int64_t* nmax, int64_t* rows);
+int64_t spx_geqr_workspace(int dtype, int64_t m, int64_t n);
+int spx_geqr(int dtype, int64_t m, int64_t n, const void* A, int64_t lda, void* R, int64_t ldr, void* workspace,
+             size_t workspace_bytes, void* stream);
+int spx_orgqr(int dtype, int64_t m, int64_t n, void* workspace, size_t workspace_bytes, const void* C, int64_t ldc,
+              void* Q, int64_t ldq, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

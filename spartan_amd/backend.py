@@ -161,6 +161,12 @@ _SIGS = {
     'spx_syrk': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
                  ctypes.c_int),
+    'spx_geqr_plan': ([ctypes.c_int, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
+    'spx_geqr_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
+    'spx_geqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    'spx_orgqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -341,6 +347,29 @@ def potrf_plan(dtype):
   v = [ctypes.c_int64(0) for _ in range(2)]
   _check(load_library().spx_potrf_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_potrf_plan')
   return tuple(int(x.value) for x in v)
+
+
+def geqr_plan(dtype, n):
+  """(nmax, r) of spx_geqr for ``n`` columns of ``dtype``, from the library:
+  the column limit and the rows one workgroup factors in LDS (r >= 2 n; 0 where
+  n is above the limit)."""
+  dt = np.dtype(dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('geqr_plan: dtype %s has no QR kernel (float32 / float64)' % dt)
+  if int(n) < 0:
+    raise ValueError('geqr_plan: negative n = %d' % n)
+  v = [ctypes.c_int64(0) for _ in range(2)]
+  _check(load_library().spx_geqr_plan(spx_dtype(dt), int(n), *[ctypes.byref(x) for x in v]), 'spx_geqr_plan')
+  return tuple(int(x.value) for x in v)
+
+
+class QrHandle:
+  """What ``geqr`` leaves for ``orgqr``: the workspace tensor (reflectors, taus,
+  signs) and the geometry it was laid out for."""
+  __slots__ = ('workspace', 'm', 'n', 'dtype')
+
+  def __init__(self, workspace, m, n, dtype):
+    self.workspace, self.m, self.n, self.dtype = workspace, m, n, dtype
 
 
 def __getattr__(name):
@@ -1398,6 +1427,54 @@ class HipBackend:
     _check(self.lib.spx_syrk(spx_dtype(dt), 1 if lower else 0, M, N, K, ctypes.c_void_p(A.data_ptr()), lda,
                              ctypes.c_void_p(B.data_ptr()), ldb, ctypes.c_void_p(C.data_ptr()), ldc, self.stream()),
            'spx_syrk')
+    if ev is not None:
+      ev[1].record()
+
+  # ------------------------------------------------------------------- qr
+  def geqr(self, A):
+    """(R, handle) of the tall or square ``A`` (m, n), m >= n (spx_geqr): R is
+    the new (n, n) upper-triangular factor with diag(R) >= 0 and +0.0 below the
+    diagonal; ``handle`` owns the workspace with the reflectors for ``orgqr``.
+    ``A`` is not written.  Asynchronous on the current stream."""
+    import torch
+    m, n, lda = self._matrix('geqr: A', A)
+    dt = np_dtype(A.dtype)
+    if m < n:
+      raise ValueError('geqr: a tall or square matrix is needed, got %s' % ((m, n),))
+    nmax, _ = geqr_plan(dt, n)
+    if n > nmax:
+      raise ValueError('geqr: %d columns are above the limit %d for %s' % (n, nmax, dt))
+    need = self.lib.spx_geqr_workspace(spx_dtype(dt), m, n)
+    if need < 0:
+      raise ValueError('geqr: bad sizes (%d, %d)' % (m, n))
+    R = torch.empty((n, n), dtype=A.dtype, device=A.device)
+    ws = torch.empty((int(need),), dtype=torch.uint8, device=A.device)
+    handle = QrHandle(ws, m, n, dt)
+    if m == 0 or n == 0:
+      return R, handle
+    ev = self._aot_events('spx_geqr')
+    _check(self.lib.spx_geqr(spx_dtype(dt), m, n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(R.data_ptr()),
+                             n, _ptr(ws), ws.numel(), self.stream()), 'spx_geqr')
+    if ev is not None:
+      ev[1].record()
+    return R, handle
+
+  def orgqr(self, handle, C, Q):
+    """``Q`` (m, n) = Q_0 ``C`` for the factorization behind ``handle``: ``C``
+    is the (n, n) seed, ``None`` for the identity (then A = Q R) (spx_orgqr).
+    Asynchronous."""
+    if not isinstance(handle, QrHandle):
+      raise ValueError('orgqr: the handle of a geqr call is needed, got %r' % (type(handle).__name__,))
+    m, n, dt = handle.m, handle.n, handle.dtype
+    _, _, ldq = self._matrix('orgqr: Q', Q, m, n, dt)
+    ldc = max(n, 1)
+    if C is not None:
+      _, _, ldc = self._matrix('orgqr: C', C, n, n, dt)
+    if m == 0 or n == 0:
+      return
+    ev = self._aot_events('spx_orgqr')
+    _check(self.lib.spx_orgqr(spx_dtype(dt), m, n, _ptr(handle.workspace), handle.workspace.numel(), _ptr(C), ldc,
+                              ctypes.c_void_p(Q.data_ptr()), ldq, self.stream()), 'spx_orgqr')
     if ev is not None:
       ev[1].record()
 

@@ -13,6 +13,7 @@ from .linalg import cho_solve, cholesky, solve_triangular
 from .map import map
 from .map_with_location import map_with_location, region_map
 from .ndarray import ndarray
+from .qr import qr
 from .reduce import reduce
 from .reshape import reshape
 from .scan import scan
