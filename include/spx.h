@@ -34,7 +34,8 @@ extern "C" {
  * spx_compact_count, spx_compact, spx_stencil_plan, spx_stencil, spx_maxpool,
  * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
- * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr */
+ * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
+ * spx_csrmm, spx_csr_todense */
 
 /* error codes */
 #define SPX_OK 0
@@ -537,6 +538,54 @@ int spx_geqr(int dtype, int64_t m, int64_t n, const void* A, int64_t lda, void* 
              size_t workspace_bytes, void* stream);
 int spx_orgqr(int dtype, int64_t m, int64_t n, void* workspace, size_t workspace_bytes, const void* C, int64_t ldc,
               void* Q, int64_t ldq, void* stream);
+
+/* ------------------------------------------------- sparse (CSR) x dense
+ * Replaces the scipy.sparse branches of the reference's dot
+ * (spartan/expr/dot.py:51, :207-231): a sparse tile times a dense block.
+ *
+ * spx_csrmm: C = alpha A B + beta C.  A is m x n in CSR -- rowptr (m + 1
+ * int64, rowptr[0] == 0, rowptr[m] == nnz), col (nnz int32 in [0, n), sorted
+ * within a row), val (nnz float32 / float64) -- B is dense row-major n x p
+ * with leading dimension ldb, C is m x p with leading dimension ldc; alpha and
+ * beta are cast to dtype.  beta == 0 overwrites C without reading it.  A group
+ * of g lanes works on a row (lanes along p first, so B's rows are read
+ * coalesced, the rest along the row's nonzeros); rows of more than T nonzeros
+ * are cut into chunks of T, one workgroup each, whose partial rows are added in
+ * chunk order.  No float atomics: a call's result is bitwise reproducible, and a
+ * row's value depends only on its own nonzeros, g and p.  g = 0 takes the g of
+ * spx_csrmm_plan for (m, nnz, p); a caller that wants the same bits for every
+ * row slab of one matrix passes one g (a power of two in 1 .. 64) to all.
+ *
+ * The workspace (spx_csrmm_workspace bytes; needed only when nnz > T) starts
+ * with the structure analysis -- the list of long rows and of their chunks,
+ * a function of rowptr alone -- followed by the call's partial rows.  With
+ * prepared == 0 the call builds the analysis (on the stream) before it uses
+ * it; with prepared != 0 it trusts what an earlier call for the same rowptr
+ * left there.  Neither case synchronises the host.
+ *
+ * spx_csrmm_plan (pure host): g, T and the rows one 256-thread workgroup
+ * covers (256 / g) for a problem.  spx_csrmm_workspace: bytes, or -1 on bad
+ * arguments (monotone in m, nnz and p).
+ *
+ * spx_csr_todense: D (m x n, leading dimension ldd) = A as a dense block:
+ * the leading n columns of every row are zero-filled, then every nonzero is
+ * stored at its place by a plain vector store (columns within a row are
+ * distinct, so no two share a destination).
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a dtype code
+ * out of range, a negative size, a leading dimension below p (n for
+ * todense), a g that is no power of two, a null pointer where it is read
+ * (col / val / B only with nnz > 0) or a short workspace; SPX_ENOTSUP for a
+ * dtype other than float32 / float64.  m == 0 or p == 0 is SPX_OK with no
+ * launch.  Additive since ABI 3. */
+int spx_csrmm_plan(int dtype, int64_t m, int64_t nnz, int64_t p, int64_t* g, int64_t* long_row,
+                   int64_t* rows_per_block);
+int64_t spx_csrmm_workspace(int dtype, int64_t m, int64_t nnz, int64_t p);
+int spx_csrmm(int dtype, int64_t m, int64_t n, int64_t p, int64_t nnz, const int64_t* rowptr, const int32_t* col,
+              const void* val, const void* B, int64_t ldb, void* C, int64_t ldc, double alpha, double beta,
+              int64_t g, void* workspace, size_t workspace_bytes, int prepared, void* stream);
+int spx_csr_todense(int dtype, int64_t m, int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* col,
+                    const void* val, void* D, int64_t ldd, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

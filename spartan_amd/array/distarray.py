@@ -286,7 +286,8 @@ def largest_value(vals):
 def create(shape, dtype=np.float64, reducer=None, tile_hint=None, sparse=False):
   """Empty DistArray with round-robin placement (distarray.py:423-483)."""
   if sparse:
-    raise NotImplementedError('sparse tiles are out of scope for the MI355X backend')
+    raise NotImplementedError('an empty sparse array is not created in place (sparse arrays are immutable): build one '
+                              'with array.sparse.from_scipy / expr.sparse_rand / sparse_diagonal / sparse_empty')
   ctx = runtime.get()
   dtype = np.dtype(dtype)
   shape = tuple(int(s) for s in shape)

@@ -167,6 +167,16 @@ _SIGS = {
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
     'spx_orgqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
+    'spx_csrmm_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P, _I64P],
+                       ctypes.c_int),
+    'spx_csrmm_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
+    'spx_csrmm': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                   ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                   ctypes.c_void_p], ctypes.c_int),
+    'spx_csr_todense': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
+                        ctypes.c_int),
     'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
     'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
     'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
@@ -370,6 +380,31 @@ class QrHandle:
 
   def __init__(self, workspace, m, n, dtype):
     self.workspace, self.m, self.n, self.dtype = workspace, m, n, dtype
+
+
+def csrmm_plan(dtype, m, nnz, p):
+  """(g, T, rows_per_block) of spx_csrmm for an (m, .) CSR matrix of ``nnz``
+  nonzeros times ``p`` dense columns, from the library: the lanes that work on
+  one row, the row length above which a row is cut into chunks of T for whole
+  workgroups, and the rows one workgroup covers."""
+  dt = np.dtype(dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('csrmm_plan: dtype %s has no sparse kernel (float32 / float64)' % dt)
+  if min(int(m), int(nnz), int(p)) < 0:
+    raise ValueError('csrmm_plan: negative size (%d, %d, %d)' % (m, nnz, p))
+  v = [ctypes.c_int64(0) for _ in range(3)]
+  _check(load_library().spx_csrmm_plan(spx_dtype(dt), int(m), int(nnz), int(p), *[ctypes.byref(x) for x in v]),
+         'spx_csrmm_plan')
+  return tuple(int(x.value) for x in v)
+
+
+class CsrWorkspace:
+  """The cached structure analysis of one CSR tile for ``csrmm``: the workspace
+  tensor and whether a call has left the long-row lists in it."""
+  __slots__ = ('buf', 'prepared')
+
+  def __init__(self):
+    self.buf, self.prepared = None, False
 
 
 def __getattr__(name):
@@ -1475,6 +1510,68 @@ class HipBackend:
     ev = self._aot_events('spx_orgqr')
     _check(self.lib.spx_orgqr(spx_dtype(dt), m, n, _ptr(handle.workspace), handle.workspace.numel(), _ptr(C), ldc,
                               ctypes.c_void_p(Q.data_ptr()), ldq, self.stream()), 'spx_orgqr')
+    if ev is not None:
+      ev[1].record()
+
+  # --------------------------------------------------------------- sparse
+  @staticmethod
+  def _csr(name, rowptr, col, val, n):
+    """(m, nnz, dtype) of the CSR triple: rowptr (m + 1,) int64, col (nnz,)
+    int32, val (nnz,) float32 / float64, all contiguous."""
+    import torch
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.numel() < 1 or not rowptr.is_contiguous():
+      raise ValueError('%s: rowptr must be a contiguous int64 vector of m + 1 entries' % name)
+    if col.dim() != 1 or col.dtype != torch.int32 or not col.is_contiguous():
+      raise ValueError('%s: col must be a contiguous int32 vector' % name)
+    if val.dtype not in (torch.float32, torch.float64):
+      raise ValueError('%s: val must be float32 / float64, not %s' % (name, val.dtype))
+    dt = np_dtype(val.dtype)
+    if val.dim() != 1 or val.numel() != col.numel() or not val.is_contiguous():
+      raise ValueError('%s: val must be a contiguous vector of col\'s length' % name)
+    if int(n) < 0 or int(n) > 2 ** 31 - 1:
+      raise ValueError('%s: %d columns are outside the int32 range' % (name, n))
+    return int(rowptr.numel()) - 1, int(col.numel()), dt
+
+  def csrmm(self, rowptr, col, val, n, B, C, alpha=1.0, beta=0.0, g=0, workspace=None):
+    """``C`` (m, p) = alpha A ``B`` + beta ``C`` for A (m, n) in CSR (spx_csrmm):
+    ``B`` (n, p) and ``C`` may be padded (unit column stride); with beta == 0
+    ``C`` is not read.  ``g`` fixes the lanes per row (0: the plan's).
+    ``workspace`` is a ``CsrWorkspace`` that keeps the structure analysis of
+    this matrix between calls (None: scratch of this call).  The columns must
+    lie in [0, n): the kernel does not check them.  Asynchronous on the current
+    stream; no host synchronisation."""
+    import torch
+    m, nnz, dt = self._csr('csrmm', rowptr, col, val, n)
+    _, p, ldb = self._matrix('csrmm: B', B, int(n), None, dt)
+    _, _, ldc = self._matrix('csrmm: C', C, m, p, dt)
+    if m == 0 or p == 0:
+      return
+    if C.data_ptr() == B.data_ptr() and B.numel():
+      raise ValueError('csrmm: C may not be B')
+    need = int(self.lib.spx_csrmm_workspace(spx_dtype(dt), m, nnz, p))
+    if need < 0:
+      raise ValueError('csrmm: bad sizes (%d, %d, %d)' % (m, nnz, p))
+    ws = workspace if workspace is not None else CsrWorkspace()
+    if ws.buf is None or ws.buf.numel() < need or ws.buf.device != val.device:
+      ws.buf, ws.prepared = torch.empty((need,), dtype=torch.uint8, device=val.device), False
+    ev = self._aot_events('spx_csrmm')
+    _check(self.lib.spx_csrmm(spx_dtype(dt), m, int(n), p, nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(B), ldb,
+                              _ptr(C), ldc, float(alpha), float(beta), int(g), _ptr(ws.buf), ws.buf.numel(),
+                              1 if ws.prepared else 0, self.stream()), 'spx_csrmm')
+    ws.prepared = True
+    if ev is not None:
+      ev[1].record()
+
+  def csr_todense(self, rowptr, col, val, n, D):
+    """``D`` (m, n), possibly padded, = the CSR matrix as a dense block
+    (spx_csr_todense).  Asynchronous."""
+    m, nnz, dt = self._csr('csr_todense', rowptr, col, val, n)
+    _, _, ldd = self._matrix('csr_todense: D', D, m, int(n), dt)
+    if m == 0 or n == 0:
+      return
+    ev = self._aot_events('spx_csr_todense')
+    _check(self.lib.spx_csr_todense(spx_dtype(dt), m, int(n), nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(D), ldd,
+                                    self.stream()), 'spx_csr_todense')
     if ev is not None:
       ev[1].record()
 

@@ -4,7 +4,7 @@ from .base import (Expr, NotShapeable, as_array, eager, evaluate, force, glom, l
                    optimized_dag)
 from .builtins import (abs, add, arange, argmax, argmin, astype, bincount, concatenate, count_nonzero,
                        count_zero, exp,
-                       ln, log, maximum, max, mean, min, minimum, multiply, ones, power, rand, randn,
+                       ln, log, maximum, max, mean, min, minimum, multiply, norm, ones, power, rand, randn,
                        size, sqrt, square, std, sub, sum, zeros)
 from .dot import dot
 from .filter import compress, take
@@ -19,6 +19,7 @@ from .reshape import reshape
 from .scan import scan
 from .slice import slice_expr
 from .sort import argpartition, argsort, partition, sort
+from .sparse import sparse_diagonal, sparse_empty, sparse_rand, todense
 from .topk import argtopk, topk
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write

@@ -70,10 +70,15 @@ class Expr:
   _members = ()
   needs_cache = True
   optimized_expr = None
+  sparse_result = False   # the value is a SparseDistArray (expr/sparse.py)
+  accepts_sparse = False  # the node knows what to do with a sparse operand
 
   def __init__(self, expr_id=None, **kw):
     for k in self._members:
-      setattr(self, k, kw.pop(k, None))
+      v = kw.pop(k, None)
+      if not self.accepts_sparse:
+        _no_sparse(v, self)
+      setattr(self, k, v)
     for k, v in kw.items():
       setattr(self, k, v)
     self.expr_id = next(_ids) if expr_id is None else expr_id
@@ -113,6 +118,8 @@ class Expr:
     deps = {}
     for k, v in self.dependencies().items():
       deps[k] = v.evaluate() if isinstance(v, Expr) else v
+      if not self.accepts_sparse:
+        _no_sparse(deps[k], self)
     value = self._evaluate(deps)
     if self.needs_cache:
       eval_cache.set(self.expr_id, value)
@@ -243,6 +250,29 @@ class Expr:
   def reshape(self, new_shape):
     from .reshape import reshape
     return reshape(self, new_shape)
+
+
+def _no_sparse(v, node):
+  """Refuse a sparse operand (an expression or a forced value, also inside a
+  list / tuple / dict) of a node that has no sparse route."""
+  if isinstance(v, (list, tuple)):
+    for x in v:
+      _no_sparse(x, node)
+  elif isinstance(v, dict):
+    for x in v.values():
+      _no_sparse(x, node)
+  elif getattr(v, 'sparse_result', False) or getattr(v, 'sparse', False):
+    raise TypeError('%s: a sparse array is not accepted here: convert it with todense() first' % type(node).__name__)
+  elif isinstance(v, CollectionExpr):
+    _no_sparse(v.vals, node)
+
+
+def _sparse_leaf(val):
+  """The sparse expression of a SparseDistArray / scipy.sparse matrix, or None."""
+  if getattr(val, 'sparse', False) is True or (type(val).__module__ or '').startswith('scipy.sparse'):
+    from .sparse import as_sparse_expr
+    return as_sparse_expr(val)
+  return None
 
 
 def _is_newaxis(i):
@@ -410,6 +440,9 @@ def eager(node):
 def lazify(val):
   if isinstance(val, Expr):
     return val
+  sp = _sparse_leaf(val)
+  if sp is not None:
+    return sp
   if isinstance(val, dict):
     return DictExpr(vals=val)
   if isinstance(val, list):
@@ -422,4 +455,7 @@ def lazify(val):
 def as_array(v):
   if isinstance(v, Expr):
     return v
+  sp = _sparse_leaf(v)
+  if sp is not None:
+    return sp
   return AsArray(val=v)

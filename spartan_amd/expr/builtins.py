@@ -199,6 +199,9 @@ def _same_dtype(input):
 
 
 def sum(x, axis=None, tile_hint=None):
+  if getattr(x, 'sparse_result', False) or getattr(x, 'sparse', False):
+    from .sparse import sparse_sum
+    return sparse_sum(x, axis)
   return reduce(x, axis=axis, dtype_fn=_same_dtype, local_reduce_fn=_sum_local, accumulate_fn=np.add,
                 tile_hint=tile_hint)
 
@@ -216,6 +219,8 @@ def min(x, axis=None, tile_hint=None):
 def mean(x, axis=None):
   """sum / count; integer inputs floor-divide as Python-2 ``np.divide`` did
   (builtins.py:527-539, SURVEY.md Appendix A pin 8)."""
+  if getattr(x, 'sparse_result', False) or getattr(x, 'sparse', False):
+    raise TypeError('mean: a sparse array is not accepted here: convert it with todense() first')
   n = int(np.prod(x.shape)) if axis is None else x.shape[axis]
   s = sum(x, axis)
   if np.dtype(x.dtype).kind in 'biu':
@@ -313,6 +318,14 @@ def square(v):
 
 def sqrt(v):
   return map(v, fn=np.sqrt)
+
+
+def norm(x):
+  """The 2-norm of a dense array: sqrt(sum(x * x)) through the fused reduce
+  (spartan/expr/builtins.py ``norm``)."""
+  from .base import as_array
+  x = as_array(x)
+  return sqrt(sum(x * x))
 
 
 def abs(v):

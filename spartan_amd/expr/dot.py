@@ -46,6 +46,7 @@ def _shape(a, b):
 
 class DotExpr(Expr):
   _members = ('matrix_a', 'matrix_b')
+  accepts_sparse = True  # dot(sparse, dense) only: expr/sparse.py
 
   def compute_shape(self):
     return _shape(self.matrix_a, self.matrix_b)
@@ -62,12 +63,22 @@ class DotExpr(Expr):
       a = LocalWrapper(a)
     if isinstance(b, np.ndarray):
       b = LocalWrapper(b)
+    if getattr(a, 'sparse', False):
+      from .sparse import sparse_dot
+      return sparse_dot(a, b)
+    if getattr(b, 'sparse', False):
+      raise TypeError('dot(dense, sparse) needs the transpose, which is not built: convert the sparse operand '
+                      'with todense() first')
     return run_dot(a, b, getattr(self, 'tile_hint', None))
 
 
 def dot(a, b, tile_hint=None):
   """Matrix / vector product of two arrays (dot.py:238-283)."""
   from ..array.distarray import DistArray
+  from .sparse import is_sparse
+  if is_sparse(b):
+    raise TypeError('dot(%s, sparse) is not supported (it needs the transpose or a sparse x sparse product): '
+                    'convert the right operand with todense() first' % ('sparse' if is_sparse(a) else 'dense'))
   if not isinstance(b, (Expr, np.ndarray, DistArray)):  # forced DistArrays stay device operands
     b = np.asarray(b)
   e = DotExpr(matrix_a=as_array(a), matrix_b=as_array(b) if not isinstance(b, np.ndarray) else b)

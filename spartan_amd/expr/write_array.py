@@ -15,8 +15,9 @@ element replaces, later writes reduce; tile.pyx:201-298):
     tile in ``_write_mapper``, :30-41), then merged on the device.
 
 ``from_numpy`` (:411-433) and ``from_file`` (.npy / .npz, dense; :380-409)
-build on the same path.  Matrix Market / sparse inputs are out of scope
-(sparse tiles are not on the MI355X path).
+build on the same path.  ``from_numpy`` of a scipy.sparse matrix ingests it as
+a sparse array (array/sparse.py); Matrix Market input (``from_file(sparse=
+True)``) stays out of scope.
 """
 import numpy as np
 
@@ -28,6 +29,10 @@ from .base import Expr, Val, lazify
 
 def from_numpy(a, tile_hint=None):
   """Upload a NumPy array into HBM tiles (each rank copies the tiles it owns)."""
+  from ..array import sparse as sparray
+  if sparray.is_scipy_sparse(a):  # any scipy.sparse format: row slabs of CSR (expr/sparse.py)
+    from .sparse import SparseVal
+    return SparseVal(val=sparray.from_scipy(a, tile_hint))
   if not isinstance(a, np.ndarray):
     raise TypeError('Expected ndarray, got: %s' % type(a))
   return Val(val=distarray.from_numpy(a, tile_hint=tile_hint))
@@ -40,7 +45,8 @@ def from_file(fn, sparse=False, tile_hint=None):
   tiles it owns; ``.npz`` members are read whole (the reference's ``arr_0``,
   or the single member).  Nothing is unpickled (``allow_pickle=False``)."""
   if sparse:
-    raise NotImplementedError('sparse inputs are not on the MI355X path')
+    raise NotImplementedError('Matrix Market / sparse file input is not built: load the file with scipy and '
+                              'pass the matrix to from_numpy')
   if fn.endswith('.npy'):
     npa = np.load(fn, mmap_mode='r', allow_pickle=False)
   elif fn.endswith('.npz'):
