@@ -112,6 +112,14 @@ def register_upload_alias(host, dev, event):
   _ALIAS['a'] = (host, dev, event)
 
 
+def drop_upload_alias(dev):
+  """Withdraw the registered alias if it is for tensor ``dev`` (its producer
+  is about to reuse the host copy)."""
+  e = _ALIAS.get('a')
+  if e is not None and e[1] is dev:
+    _ALIAS.clear()
+
+
 def _take_alias(arr, device):
   host, dev, ev = _ALIAS.pop('a')
   if dev.device != device or arr.dtype != host.dtype or arr.size != host.size or tuple(dev.shape) != arr.shape:
@@ -217,6 +225,14 @@ def attach_shadow(t, host, event):
   once ``event`` has completed."""
   import weakref
   _SHADOWS[id(t)] = (weakref.ref(t), t._version, host, event)
+
+
+def drop_shadow(t):
+  """Withdraw tensor ``t``'s shadow, if it has one (its producer is about to
+  reuse the host copy)."""
+  e = _SHADOWS.get(id(t))
+  if e is not None and e[0]() is t:
+    del _SHADOWS[id(t)]
 
 
 def _take_shadow(t):

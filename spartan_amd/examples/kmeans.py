@@ -29,10 +29,14 @@ centre sums are SUMMED over tiles, where the reference's reducer-less map2
 keeps the last tile's; empty clusters are reseeded from a
 seeded generator instead of the global ``np.random``.
 """
+import os
+import types
+import weakref
+
 import numpy as np
 
 from .. import backend, comm, expr, runtime
-from ..array import distarray, extent as ext
+from ..array import distarray, extent as ext, transfer
 from ..expr.join import register_argmin_fusion, register_join
 
 
@@ -70,40 +74,37 @@ def _replicated_f64(array):
   return backend.get().contiguous(got[ctx.rank], np.float64)
 
 
-# X's row blocks for the joins, kept across iterations at world size 1 (an
-# iterative driver passes the same forced X every time; with more ranks the
-# gather is a collective every rank must enter, so nothing is cached): valid
-# while X lives (a weak reference) and every local tile tensor is the same
-# object -- the rows are views of the tiles.  One entry.
-_ROWS = {}
-
-
 def _row_blocks(X, ncols):
   """[(owner rank, row extent over all columns)] of X's row blocks, and
-  {index: device tensor} of the local ones (gathered when X is column-split)."""
-  import weakref
+  {index: device tensor} of the local ones (gathered when X is column-split).
+  Kept across iterations at world size 1 (_PIPE.rows: an iterative driver passes
+  the same forced X every time; with more ranks the gather is a collective
+  every rank must enter, so nothing is cached)."""
   ctx = runtime.get()
   local = getattr(X, 'local', None)
-  stamp = None
+  tiles = None
   if ctx.world_size == 1 and isinstance(local, dict) and not getattr(X, 'replicated', False):
-    stamp = (ncols,) + tuple((tuple(ex.ul), id(t._data)) for ex, t in local.items())
-    hit = _ROWS.get('x')
-    if hit is not None and hit[0]() is X and hit[1] == stamp:
-      return hit[2], hit[3]
+    tiles = [(tuple(ex.ul), t._data) for ex, t in local.items()]
+    hit = _PIPE.rows
+    if (hit is not None and hit[0]() is X and hit[1] == ncols and len(hit[2]) == len(tiles)
+        and all(a[0] == b[0] and a[1] is b[1] for a, b in zip(hit[2], tiles))):
+      return hit[3], hit[4]
   rows = sorted({(ex.ul[0], ex.lr[0]): w for ex, w in X.tiles.items()}.items())
   blocks = [(ctx.owner(w) if w != -1 else ctx.rank,
              ext.create((r0, 0), (r1, ncols), X.shape) if len(X.shape) == 2 else ext.create((r0,), (r1,), X.shape))
             for (r0, r1), w in rows]
   got = distarray.gather_regions(X, [(region, dst) for dst, region in blocks])
-  _ROWS.clear()
-  if stamp is not None:
-    try:
-      ref = weakref.ref(X, lambda _r: _ROWS.clear())
-    except TypeError:
-      ref = None
-    if ref is not None:
-      _ROWS['x'] = (ref, stamp, blocks, got)
+  _PIPE.rows = None if tiles is None else (weakref.ref(X, _PIPE.drop_rows), ncols, tiles, blocks, got)
   return blocks, got
+
+
+def _local_rows(X, ncols):
+  """X's row blocks (_row_blocks; collective), and an iterator over this
+  rank's: (index, region, the block's points with unit column stride)."""
+  rank, be = runtime.get().rank, backend.get()
+  blocks, got = _row_blocks(X, ncols)
+  mine = ((qi, region, got[qi]) for qi, (src, region) in enumerate(blocks) if src == rank)
+  return blocks, ((qi, region, p if p.stride(-1) == 1 else be.contiguous(p)) for qi, region, p in mine)
 
 
 def _deliver_full(target, full):
@@ -134,19 +135,13 @@ def _dist_join(kind, arrays, axes, fn_kw, target):
   be = backend.get()
   c = _replicated_f64(C)
   K, D = c.shape
-  blocks, got = _row_blocks(X, D)
-  updates = []
-  for qi, (src, region) in enumerate(blocks):
-    tex = ext.create((region.ul[0], 0), (region.lr[0], K), target.shape)
-    t = None
-    if src == ctx.rank:
-      pts = got[qi]
-      if pts.stride(-1) != 1:
-        pts = be.contiguous(pts)
-      t = torch.empty(tex.shape, dtype=backend.torch_dtype(target.dtype), device=ctx.device)
-      be.cdist(pts, c, t)
-    updates.append((qi, tex, src, t))
-  _scatter_updates(target, updates)
+  blocks, rows = _local_rows(X, D)
+  dist = {}
+  for qi, region, pts in rows:
+    dist[qi] = torch.empty((region.shape[0], K), dtype=backend.torch_dtype(target.dtype), device=ctx.device)
+    be.cdist(pts, c, dist[qi])
+  _scatter_updates(target, [(qi, ext.create((r.ul[0], 0), (r.lr[0], K), target.shape), src, dist.get(qi))
+                            for qi, (src, r) in enumerate(blocks)])
 
 
 def _count_join(kind, arrays, axes, fn_kw, target):
@@ -155,16 +150,11 @@ def _count_join(kind, arrays, axes, fn_kw, target):
   be = backend.get()
   K = int(fn_kw['centers_count'])
   labels = arrays[0]
-  pre = _take_step(_STEP.get('X'), labels, K, 'counts')
+  pre = _PIPE.take(labels, K)
   if pre is not None:
     comm.all_reduce(pre, 'sum')
     _deliver_full(target, pre)
-    _DT['cdt'] = np.dtype(target.dtype)
-    _early_shadow('counts', target)
-    _RED.clear()
-    if len(target.local) == 1:  # the counts as the host will read them, for _speculate
-      (_ex, tile), = target.local.items()
-      _RED.update(labels=labels, counts=tile.data)
+    _PIPE.counts_delivered(target)
     return
   counts = torch.zeros((K,), dtype=torch.int64, device=ctx.device)
   for ex, tile in labels.local.items():
@@ -181,39 +171,24 @@ def _center_join(kind, arrays, axes, fn_kw, target):
   K = int(fn_kw['centers_count'])
   X, labels = arrays
   D = X.shape[1]
-  pre = _take_step(X, labels, K, 'sums')
+  pre = _PIPE.take(labels, K, X)
   if pre is not None:  # the fused step of this labels array already summed X
     comm.all_reduce(pre, 'sum')
     _deliver_full(target, pre)
-    _DT['sdt'] = np.dtype(target.dtype)
-    _early_shadow('sums', target)
-    if _NEXT['on'] and not _SPEC:  # (not queued early, _speculate_early)
-      _speculate(X, labels, K, target)
+    _PIPE.sums_delivered(X, K, target)
     return
   sums = torch.zeros((K, D), dtype=torch.float64, device=ctx.device)
   counts = torch.zeros((K,), dtype=torch.int64, device=ctx.device)
-  blocks, got = _row_blocks(X, D)
+  blocks, rows = _local_rows(X, D)
   lab_blocks = distarray.gather_regions(labels, [(ext.create((r.ul[0],), (r.lr[0],), labels.shape)
                                                   if len(labels.shape) == 1 else
                                                   ext.create((r.ul[0], 0), (r.lr[0], labels.shape[1]), labels.shape),
                                                   dst) for dst, r in blocks])
-  for qi, (src, region) in enumerate(blocks):
-    if src != ctx.rank:
-      continue
-    pts = got[qi]
-    if pts.stride(-1) != 1:
-      pts = be.contiguous(pts)
+  for qi, _region, pts in rows:
     lab = be.contiguous(lab_blocks[qi], np.int64).reshape(-1)
     be.kmeans_accumulate(pts, lab, sums, counts, zero_first=False)
   comm.all_reduce(sums, 'sum')
   _deliver_full(target, sums)
-
-
-# The last fused assignment's per-rank centre sums and counts (one entry):
-# argmin(outer(X, C)) runs spx_kmeans_step, which produces the iteration's
-# sums and counts from the same single pass over X, and the centre / count
-# joins of THAT labels array over THAT X take them instead of reading X again.
-_STEP = {}
 
 
 def _step_domain(X, K):
@@ -229,8 +204,9 @@ def _assign_fused(arrays, fn_kw, target, dist_dtype):
   points: map2 / outer dtype None -> arrays[0].dtype); spx_kmeans_assign per
   X row block gives the argmin of exactly those values (first index on
   ties, first NaN wins) without materialising them.  In spx_kmeans_step's
-  domain the same labels come from the fused step, which also leaves this
-  rank's centre sums and counts in _STEP for _center_join / _count_join."""
+  domain the same labels come from the fused step, whose centre sums and
+  counts (of the same single pass over X) the centre / count joins of THAT
+  labels array over THAT X take (_PIPE.hand_off) instead of reading X again."""
   import torch
   from ..expr.join import _scatter_updates
   X, C = arrays
@@ -238,55 +214,48 @@ def _assign_fused(arrays, fn_kw, target, dist_dtype):
   be = backend.get()
   c = _replicated_f64(C)
   K, D = c.shape
-  blocks, got = _row_blocks(X, D)
+  blocks, rows = _local_rows(X, D)
   fused = _step_domain(X, K)
-  spec = _take_spec(X, K, c, dist_dtype) if fused else None
-  _STEP.clear()
-  if fused:  # the first local block's step writes them (zero_first), the others add
-    sums = torch.empty((K, D), dtype=torch.float64, device=ctx.device)
-    counts = torch.empty((K,), dtype=torch.int64, device=ctx.device)
-    first = True
-  updates = []
-  for qi, (src, region) in enumerate(blocks):
-    tex = ext.create((region.ul[0],), (region.lr[0],), target.shape)
-    lab = None
-    if src == ctx.rank:
-      pts = got[qi]
-      if pts.stride(-1) != 1:
-        pts = be.contiguous(pts)
-      if spec is not None:  # the step queued for these very centres (_speculate)
-        lab = spec['labs'][qi]
-        first = False
-      elif fused:
-        lab = torch.empty((tex.shape[0],), dtype=torch.int64, device=ctx.device)
-        be.kmeans_step(pts, c, lab, sums, counts, zero_first=first, dist_dtype=dist_dtype)
-        first = False
-      else:
-        lab = torch.empty((tex.shape[0],), dtype=torch.int64, device=ctx.device)
-      if not fused:
-        be.kmeans_assign(pts, c, lab, dist_dtype=dist_dtype)
-    updates.append((qi, tex, src, lab))
-  _scatter_updates(target, updates)
+  spec = _PIPE.take_queued(X, K, c, dist_dtype) if fused else None
+  if spec is not None:  # the step queued for these very centres (_speculate)
+    labs, sums, counts = spec.labs, spec.sums, spec.counts
+  elif fused:
+    labs, sums, counts = _fused_step(rows, c, dist_dtype)
+  else:
+    labs = {}
+    for qi, region, pts in rows:
+      labs[qi] = torch.empty((region.shape[0],), dtype=torch.int64, device=ctx.device)
+      be.kmeans_assign(pts, c, labs[qi], dist_dtype=dist_dtype)
+  _scatter_updates(target, [(qi, ext.create((r.ul[0],), (r.lr[0],), target.shape), src, labs.get(qi))
+                            for qi, (src, r) in enumerate(blocks)])
   if fused:
-    if spec is not None:
-      sums, counts = spec['sums'], spec['counts']
-    elif first:  # no local row block on this rank
-      sums.zero_()
-      counts.zero_()
-    _STEP.update(labels=target, X=X, K=K, sums=sums, counts=counts, dd=dist_dtype)
-    _EARLY.clear()
-    if spec is not None and _spec_on():
-      # (the loop's last iteration queues nothing, but still stages the
-      # copies: its gloms and the upload of the final centres then need no
-      # round trip of their own)
-      _speculate_early(X, K, sums, counts, dist_dtype, queue=_NEXT['on'])
+    _PIPE.hand_off(X, target, K, sums, counts, dist_dtype, adopted=spec is not None)
+
+
+def _fused_step(rows, c, dist_dtype):
+  """spx_kmeans_step for centres c (device fp64) over this rank's row blocks (rows:
+  _local_rows), in fresh buffers: ({block index: labels}, centre sums, counts)."""
+  import torch
+  be = backend.get()
+  # the first local block's step writes them (zero_first), the others add
+  sums = torch.empty(tuple(c.shape), dtype=torch.float64, device=c.device)
+  counts = torch.empty((c.shape[0],), dtype=torch.int64, device=c.device)
+  labs = {}
+  for qi, _region, pts in rows:
+    lab = torch.empty((pts.shape[0],), dtype=torch.int64, device=c.device)
+    be.kmeans_step(pts, c, lab, sums, counts, zero_first=not labs, dist_dtype=dist_dtype)
+    labs[qi] = lab
+  if not labs:  # no local row block on this rank
+    sums.zero_()
+    counts.zero_()
+  return labs, sums, counts
 
 
 # Speculation (world size 1; SPARTAN_KMEANS_SPECULATE, default on).  The
 # reference's loop reads the counts and the centre sums back to the host,
 # divides there and uploads the new centres (k_means_.py:140-150): the GPU
 # idles for that round trip and for the building of the next iteration's
-# expressions.  While KMeans.fit has an iteration to go (_NEXT), the centre
+# expressions.  While KMeans.fit has an iteration to go (following), the centre
 # join, once the sums are all-reduced and delivered, (1) computes the next
 # centres on the device exactly as the host will (the sums and counts rounded
 # to the joins' target dtypes, divided in NumPy's result dtype), (2) copies
@@ -300,160 +269,188 @@ def _assign_fused(arrays, fn_kw, target, dist_dtype):
 # the sequential loop.  (A side stream cannot overlap: k_kmeans_pp holds every
 # CU's register file and LDS, so any other kernel -- the runtime's copy
 # kernels too -- waits for it.)
-_RED = {}           # the last fused step's all-reduced counts (from _count_join)
-_DT = {}            # the dtypes the count / centre joins delivered in (the host reads them so)
-_EARLY = {}         # host copies staged by _speculate_early for this iteration's joins
-_SPEC = {}          # the queued step (one entry)
-_NEXT = {'on': False}
-_PIN = {}           # pinned staging for the shadows
 SPEC_STATS = {'queued': 0, 'adopted': 0, 'dropped': 0}
 
 
 def _spec_on():
-  import os
   ctx = runtime.get()
   return (ctx.world_size == 1 and ctx.device.type == 'cuda'
           and os.environ.get('SPARTAN_KMEANS_SPECULATE', '1') != '0')
 
 
-def _pinned(key, shape, tdt):
-  import torch
-  hp = _PIN.get(key)
-  if hp is None or tuple(hp.shape) != tuple(shape) or hp.dtype != tdt:
-    hp = _PIN[key] = torch.empty(tuple(shape), dtype=tdt, pin_memory=True)
-  return hp
+class _Pinned:
+  """One pinned staging buffer, and the device tensor whose host shadow or
+  upload alias (array/transfer.py) reads from it until somebody takes it."""
+  buf = lent = None
+
+  def stage(self, t):
+    """Start t's copy into the buffer (withdrawing what still reads from it): its host view."""
+    import torch
+    self.withdraw()
+    if self.buf is None or tuple(self.buf.shape) != tuple(t.shape) or self.buf.dtype != t.dtype:
+      self.buf = torch.empty(tuple(t.shape), dtype=t.dtype, pin_memory=True)
+    self.buf.copy_(t, non_blocking=True)
+    return self.buf.numpy()
+
+  def withdraw(self):
+    transfer.drop_shadow(self.lent)  # (each drops an entry for THIS tensor only)
+    transfer.drop_upload_alias(self.lent)
+    self.lent = None
 
 
-def _queue(X, K, cn, dd):
-  """Queue the fused step of X for centres cn (device fp64) on the current
-  stream: labels, sums, counts in fresh buffers, recorded in _SPEC."""
-  import torch
-  ctx = runtime.get()
-  be = backend.get()
-  D = X.shape[1]
-  blocks, got = _row_blocks(X, D)
-  s2 = torch.empty((K, D), dtype=torch.float64, device=ctx.device)
-  c2 = torch.empty((K,), dtype=torch.int64, device=ctx.device)
-  labs = {}
-  first = True
-  for qi, (src, _r) in enumerate(blocks):
-    if src != ctx.rank:
-      continue
-    pts = got[qi]
-    if pts.stride(-1) != 1:
-      pts = be.contiguous(pts)
-    lab = torch.empty((pts.shape[0],), dtype=torch.int64, device=ctx.device)
-    be.kmeans_step(pts, cn, lab, s2, c2, zero_first=first, dist_dtype=dd)
-    first = False
-    labs[qi] = lab
-  if first:
-    s2.zero_()
-    c2.zero_()
-  _SPEC.update(X=X, K=K, dd=dd, cn=cn, labs=labs, sums=s2, counts=c2)
-  SPEC_STATS['queued'] += 1
+class _Pipeline:
+  """What the four joins hand to each other and to KMeans.fit.  One instance
+  (_PIPE): the joins are registered callbacks, and a loop written by hand
+  gets the same one-pass hand-off as KMeans.fit.  X and the label arrays are
+  referred to weakly only: nothing here extends their lives."""
+
+  def __init__(self):
+    # for the process (reset() keeps them: a warm-up fit pays for them)
+    self.pin_sums, self.pin_counts, self.pin_centres = _Pinned(), _Pinned(), _Pinned()
+    # the row-block cache, one entry (weak X, ncols, [(tile origin, tile tensor)],
+    # blocks, rows): valid while X lives and every local tile tensor is the same
+    # object (the rows are views of them); reset() keeps it for the next fit of X
+    self.rows = None
+    self.reset()
+
+  def reset(self):
+    """Drop one iteration's hand-off and the queued step and withdraw what was
+    registered here and never taken (KMeans.fit: on entry, and however it ends)."""
+    # the last fused assignment's per-rank centre sums and counts, each taken
+    # once by the join of THAT labels array (over THAT X)
+    self.step_X = self.step_labels = self.step_K = self.step_dd = self.step_sums = self.step_counts = None
+    self.red_counts = None  # its all-reduced counts as the host will read them (count join -> _speculate)
+    # the dtypes the count / centre joins delivered in (the host reads them so)
+    self.sums_dtype = self.counts_dtype = None
+    # (host copy, event) staged by _speculate_early for this iteration's joins
+    self.early_sums = self.early_counts = None
+    # the queued step (weak X, K, distance dtype, centres cn, {block index:
+    # labels}, sums, counts), until the next assignment takes or drops it
+    self.queued = None
+    self.following = False  # "another iteration follows": set by KMeans.fit around its two gloms
+    for pin in (self.pin_sums, self.pin_counts, self.pin_centres):
+      pin.withdraw()
+
+  def drop_rows(self, _ref):
+    self.rows = None  # (the cached X died)
+
+  def hand_off(self, X, labels, K, sums, counts, dd, adopted):
+    """From the fused assignment: this rank's sums and counts of (X, labels)."""
+    self.step_X, self.step_labels = weakref.ref(X), weakref.ref(labels)
+    self.step_K, self.step_dd, self.step_sums, self.step_counts = K, dd, sums, counts
+    self.early_sums = self.early_counts = self.red_counts = None
+    if adopted and _spec_on():
+      self._speculate_early(X, K, sums, counts, dd)
+
+  def take(self, labels, K, X=None):
+    """This rank's fused counts for labels (given X: the centre sums for (X, labels)), once each, or None."""
+    if self.step_labels is None or self.step_labels() is not labels or self.step_K != K \
+        or X is not None and self.step_X() is not X:
+      return None
+    if X is None:
+      pre, self.step_counts = self.step_counts, None
+    else:
+      pre, self.step_sums = self.step_sums, None
+    return pre
+
+  def counts_delivered(self, target):
+    self.counts_dtype = np.dtype(target.dtype)
+    self._early_shadow(self.pin_counts, self.early_counts, target)
+    self.early_counts = None
+    if len(target.local) == 1:  # the counts as the host will read them, for _speculate
+      (_ex, tile), = target.local.items()
+      self.red_counts = tile.data
+
+  def sums_delivered(self, X, K, target):
+    self.sums_dtype = np.dtype(target.dtype)
+    self._early_shadow(self.pin_sums, self.early_sums, target)
+    self.early_sums = None
+    if self.following and self.queued is None:  # (not queued early, _speculate_early)
+      self._speculate(X, K, target)
+
+  def _early_shadow(self, pin, staged, target):
+    """Attach the early-staged host copy to target's tile (if dtype and shape match what was staged)."""
+    if staged is None or len(target.local) != 1:
+      return
+    host, ev = staged
+    (_ex, tile), = target.local.items()
+    tt = tile.data
+    if np.dtype(target.dtype) == host.dtype and tuple(tt.shape) == tuple(host.shape):
+      transfer.attach_shadow(tt, host, ev)
+      pin.lent = tt
+
+  def _speculate(self, X, K, target):
+    """At the centre join (no step queued yet: the loop's first iteration, or
+    after a dropped one): queue the next step behind a pinned copy of the sums
+    the host is about to glom (a host shadow of the target tile)."""
+    if not _spec_on() or self.red_counts is None or len(target.local) != 1:
+      return
+    counts, self.red_counts = self.red_counts, None
+    (_ex, tile), = target.local.items()
+    tt = tile.data  # the centre sums as the host will read them (the target's dtype)
+    if tuple(tt.shape) != (K, X.shape[1]) or tuple(counts.shape) != (K,):
+      return
+    self._stage(X, K, tt, counts, self.step_dd, shadow_now=True, queue=True)
+
+  def _speculate_early(self, X, K, sums, counts, dd):
+    """At the adoption of a queued step (world size 1: its sums and counts ARE the
+    values this iteration's joins deliver): queue the step after it right away,
+    computing its centres as the host will (the joins' target dtypes of the last
+    iteration, NumPy's result dtype), and stage pinned copies of what the host will
+    glom -- the counts, the sums in the centre target's dtype -- and of those centres,
+    all before the step, so that neither the gloms nor the upload of the centres wait
+    behind it.  The joins attach the copies as host shadows of their target tiles."""
+    if self.sums_dtype is None or self.counts_dtype is None:
+      return
+    # (the loop's last iteration queues nothing, but still stages the copies: its gloms
+    # and the upload of the final centres then need no round trip of their own)
+    st, ct = sums.to(backend.torch_dtype(self.sums_dtype)), counts.to(backend.torch_dtype(self.counts_dtype))
+    self._stage(X, K, st, ct, dd, shadow_now=False, queue=self.following)
+
+  def _stage(self, X, K, st, ct, dd, shadow_now, queue):
+    """The next centres from sums st / counts ct (device, in the dtypes the joins
+    deliver), divided as the host will; pinned copies of st (its shadow now, or
+    staged with ct's for the joins to attach) and of the centres; then the step."""
+    import torch
+    rdt = backend.torch_dtype(np.result_type(backend.np_dtype(st.dtype), backend.np_dtype(ct.dtype)))
+    cn = (st.to(rdt) / ct.to(rdt).view(K, 1)).to(torch.float64)
+    hs = self.pin_sums.stage(st)
+    hk = None if shadow_now else self.pin_counts.stage(ct)
+    # the centres the host will compute, to host too: its from_numpy of them
+    # then takes cn itself instead of a synchronous upload queued behind the
+    # step (transfer.register_upload_alias; bit-identical or not taken)
+    hc = self.pin_centres.stage(cn)
+    ev = torch.cuda.Event()
+    ev.record()
+    if shadow_now:
+      transfer.attach_shadow(st, hs, ev)
+      self.pin_sums.lent = st
+    else:
+      self.early_sums, self.early_counts = (hs, ev), (hk, ev)
+    transfer.register_upload_alias(hc, cn, ev)
+    self.pin_centres.lent = cn
+    if queue:
+      labs, sums, counts = _fused_step(_local_rows(X, X.shape[1])[1], cn, dd)  # on the current stream
+      self.queued = types.SimpleNamespace(X=weakref.ref(X), K=K, dd=dd, cn=cn, labs=labs, sums=sums, counts=counts)
+      SPEC_STATS['queued'] += 1
+
+  def take_queued(self, X, K, c, dist_dtype):
+    """The queued step if it ran for exactly these centres (bit for bit), X, K
+    and distance dtype, else None."""
+    import torch
+    sp, self.queued = self.queued, None
+    if sp is None:
+      return None
+    # (the comparison's host sync waits for the queued step: the GPU is busy)
+    if not (sp.X() is X and sp.K == K and sp.dd == dist_dtype and tuple(c.shape) == tuple(sp.cn.shape)
+            and torch.equal(c.contiguous().view(torch.int64), sp.cn.view(torch.int64))):
+      SPEC_STATS['dropped'] += 1
+      return None
+    SPEC_STATS['adopted'] += 1
+    return sp
 
 
-def _speculate(X, labels, K, target):
-  """At the centre join (no step queued yet: the loop's first iteration, or
-  after a dropped one): queue the next step behind a pinned copy of the sums
-  the host is about to glom (a host shadow of the target tile)."""
-  import torch
-  _SPEC.clear()
-  if not _spec_on() or _RED.get('labels') is not labels or _STEP.get('labels') is not labels \
-      or len(target.local) != 1:
-    return
-  from ..array import transfer
-  counts = _RED.pop('counts')
-  (_ex, tile), = target.local.items()
-  tt = tile.data  # the centre sums as the host will read them (the target's dtype)
-  if tuple(tt.shape) != (K, X.shape[1]) or tuple(counts.shape) != (K,):
-    return
-  rdt = backend.torch_dtype(np.result_type(backend.np_dtype(tt.dtype), backend.np_dtype(counts.dtype)))
-  cn = (tt.to(rdt) / counts.to(rdt).view(K, 1)).to(torch.float64)
-  hp = _pinned('sums', tt.shape, tt.dtype)
-  hp.copy_(tt, non_blocking=True)
-  # the centres the host will compute, to host too: its from_numpy of them
-  # then takes cn itself instead of a synchronous upload queued behind the
-  # step (transfer.register_upload_alias; bit-identical or not taken)
-  hc = _pinned('cn', cn.shape, torch.float64)
-  hc.copy_(cn, non_blocking=True)
-  ev = torch.cuda.Event()
-  ev.record()
-  transfer.attach_shadow(tt, hp.numpy(), ev)
-  transfer.register_upload_alias(hc.numpy(), cn, ev)
-  _queue(X, K, cn, _STEP.get('dd'))
-
-
-def _speculate_early(X, K, sums, counts, dd, queue=True):
-  """At the adoption of a queued step (world size 1: its sums and counts ARE
-  the values this iteration's joins deliver): queue the step after it right
-  away, computing its centres as the host will (the joins' target dtypes of
-  the last iteration, NumPy's result dtype), and stage pinned copies of what
-  the host will glom -- the counts, the sums in the centre target's dtype --
-  and of those centres, all before the step, so that neither the gloms nor
-  the upload of the centres wait behind it.  The joins attach the copies as
-  host shadows of their target tiles (_EARLY)."""
-  import torch
-  from ..array import transfer
-  sdt, cdt = _DT.get('sdt'), _DT.get('cdt')
-  if sdt is None or cdt is None:
-    return
-  tdt = backend.torch_dtype
-  rdt = tdt(np.result_type(sdt, cdt))
-  st = sums.to(tdt(sdt))
-  ct = counts.to(tdt(cdt))
-  cn = (st.to(rdt) / ct.to(rdt).view(K, 1)).to(torch.float64)
-  hs = _pinned('e_sums', st.shape, st.dtype)
-  hk = _pinned('e_counts', ct.shape, ct.dtype)
-  hc = _pinned('cn', cn.shape, torch.float64)
-  hs.copy_(st, non_blocking=True)
-  hk.copy_(ct, non_blocking=True)
-  hc.copy_(cn, non_blocking=True)
-  ev = torch.cuda.Event()
-  ev.record()
-  _EARLY.clear()
-  _EARLY.update(sums=(hs.numpy(), ev, sdt), counts=(hk.numpy(), ev, cdt))
-  transfer.register_upload_alias(hc.numpy(), cn, ev)
-  if queue:
-    _queue(X, K, cn, dd)
-
-
-def _early_shadow(what, target):
-  """Attach the early-staged host copy of ``what`` to target's tile (if the
-  dtype and shape match what was staged)."""
-  from ..array import transfer
-  e = _EARLY.pop(what, None)
-  if e is None or len(target.local) != 1:
-    return
-  host, ev, dt = e
-  (_ex, tile), = target.local.items()
-  tt = tile.data
-  if np.dtype(target.dtype) == dt and tuple(tt.shape) == tuple(host.shape):
-    transfer.attach_shadow(tt, host, ev)
-
-
-def _take_spec(X, K, c, dist_dtype):
-  """The queued step if it ran for exactly these centres (bit for bit), X, K
-  and distance dtype, else None."""
-  import torch
-  sp = dict(_SPEC)
-  _SPEC.clear()
-  if not sp:
-    return None
-  # (the comparison's host sync waits for the queued step: the GPU is busy)
-  if not (sp['X'] is X and sp['K'] == K and sp['dd'] == dist_dtype and tuple(c.shape) == tuple(sp['cn'].shape)
-          and torch.equal(c.contiguous().view(torch.int64), sp['cn'].view(torch.int64))):
-    SPEC_STATS['dropped'] += 1
-    return None
-  SPEC_STATS['adopted'] += 1
-  return sp
-
-
-def _take_step(X, labels, K, what):
-  """This rank's fused sums / counts for (X, labels), once each, or None."""
-  if _STEP.get('labels') is labels and _STEP.get('X') is X and _STEP.get('K') == K and what in _STEP:
-    return _STEP.pop(what)
-  return None
+_PIPE = _Pipeline()
 
 
 register_join(kmeans_dist_mapper, _dist_join)
@@ -479,38 +476,41 @@ class KMeans(object):
     if implementation != 'outer':
       raise NotImplementedError('implementation %r: "outer" (default) and "broadcast" are on the path'
                                 % implementation)
-    num_dim = X.shape[1]
-    rng = np.random.default_rng(self.seed)
-    labels = expr.zeros((X.shape[0], 1), dtype=np.int64)
-    if centers is None:
-      centers = expr.rand(self.n_clusters, num_dim)
-    elif isinstance(centers, np.ndarray):
-      centers = expr.from_numpy(centers)
-    for i in range(self.n_iter):
-      self.assign_centers_ = centers  # the centres this iteration's labels are assigned against
-      distances = expr.outer((X, centers), (0, 0), fn=kmeans_dist_mapper,
-                             shape=(X.shape[0], centers.shape[0]))
-      labels = expr.argmin(distances, axis=1)
-      counts = expr.map2(labels, 0, fn=kmeans_count_mapper, fn_kw={'centers_count': self.n_clusters},
-                         shape=(centers.shape[0],))
-      new_centers = expr.map2((X, labels), (0, 0), fn=kmeans_center_mapper,
-                              fn_kw={'centers_count': self.n_clusters},
-                              shape=(centers.shape[0], centers.shape[1]))
-      # (another iteration follows: the centre join may queue it, _speculate)
-      _NEXT['on'] = i + 1 < self.n_iter
-      try:
+    _PIPE.reset()
+    try:
+      num_dim = X.shape[1]
+      rng = np.random.default_rng(self.seed)
+      labels = expr.zeros((X.shape[0], 1), dtype=np.int64)
+      if centers is None:
+        centers = expr.rand(self.n_clusters, num_dim)
+      elif isinstance(centers, np.ndarray):
+        centers = expr.from_numpy(centers)
+      for i in range(self.n_iter):
+        self.assign_centers_ = centers  # the centres this iteration's labels are assigned against
+        distances = expr.outer((X, centers), (0, 0), fn=kmeans_dist_mapper,
+                               shape=(X.shape[0], centers.shape[0]))
+        labels = expr.argmin(distances, axis=1)
+        counts = expr.map2(labels, 0, fn=kmeans_count_mapper, fn_kw={'centers_count': self.n_clusters},
+                           shape=(centers.shape[0],))
+        new_centers = expr.map2((X, labels), (0, 0), fn=kmeans_center_mapper,
+                                fn_kw={'centers_count': self.n_clusters},
+                                shape=(centers.shape[0], centers.shape[1]))
+        # (another iteration follows: the centre join may queue it, _speculate;
+        # if a glom raises, fit's reset() lowers the flag)
+        _PIPE.following = i + 1 < self.n_iter
         counts = counts.optimized().glom()
         centers = new_centers.optimized().glom()
-      finally:
-        _NEXT['on'] = False
-      zcount_indices = (counts == 0).reshape(self.n_clusters)
-      if np.any(zcount_indices):
-        n_points = np.count_nonzero(zcount_indices)
-        counts[zcount_indices] = 1
-        centers[zcount_indices, :] = rng.standard_normal((n_points, num_dim))
-      centers = centers / counts.reshape(centers.shape[0], 1)
-      centers = expr.from_numpy(centers)
-    return centers.glom(), labels
+        _PIPE.following = False
+        zcount_indices = (counts == 0).reshape(self.n_clusters)
+        if np.any(zcount_indices):
+          n_points = np.count_nonzero(zcount_indices)
+          counts[zcount_indices] = 1
+          centers[zcount_indices, :] = rng.standard_normal((n_points, num_dim))
+        centers = centers / counts.reshape(centers.shape[0], 1)
+        centers = expr.from_numpy(centers)
+      return centers.glom(), labels
+    finally:  # nothing of this fit outlives it (X, its labels, a queued step, untaken shadows)
+      _PIPE.reset()
 
   def _fit_broadcast(self, X, centers):
     """k_means_.py:153-187: the same iteration written with broadcasting

@@ -976,8 +976,14 @@ def test_kmeans_api_speculation_identical(ex, case, monkeypatch):
   bit-identical centres.  Centres and labels must equal the run with
   SPARTAN_KMEANS_SPECULATE=0; 'plain' / 'd64' adopt every queued step,
   'empty' (a centre no point is nearest to: the host reseeds it) drops the
-  one queued for the reseeded centres."""
+  one queued for the reseeded centres.  The fit leaves no host shadow or
+  upload alias registered and keeps neither X nor the labels alive."""
+  import gc
+  import weakref
+  from spartan_amd.array import transfer
   from spartan_amd.examples import kmeans as KM
+  from spartan_amd.expr import plan_cache
+  from spartan_amd.expr.base import eval_cache
   expr, setw = ex
   setw(1)
   D, K, n = (64, 32, 30000) if case == 'd64' else (128, 64, 40000)
@@ -993,6 +999,8 @@ def test_kmeans_api_speculation_identical(ex, case, monkeypatch):
     c, lab = KM.KMeans(K, 3).fit(X, c0)
     stats = {k: KM.SPEC_STATS[k] - before[k] for k in before}
     runs.append((c, lab.glom(), stats))
+  # nothing the speculating fit registered is left for a later download / upload to take
+  assert not transfer._SHADOWS and not transfer._ALIAS
   (ca, la, sa), (cb, lb, sb) = runs
   assert np.array_equal(ca.view(np.int64), cb.view(np.int64))
   np.testing.assert_array_equal(la, lb)
@@ -1002,6 +1010,13 @@ def test_kmeans_api_speculation_identical(ex, case, monkeypatch):
     assert sb['dropped'] >= 1 and sb['adopted'] + sb['dropped'] == 2, sb
   else:
     assert sb['adopted'] == 2, sb
+  # ... and the fit keeps neither X nor its labels alive
+  wx, wl = weakref.ref(X), weakref.ref(lab.force())
+  del X, lab
+  eval_cache.clear()
+  plan_cache.clear()
+  gc.collect()
+  assert wx() is None and wl() is None
 
 
 @pytest.mark.parametrize('dt', [np.float32, np.float64])

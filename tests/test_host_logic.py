@@ -437,6 +437,143 @@ def test_kmeans_api_one_pass(host_ctx):
   np.testing.assert_array_equal(l1.glom(), l2.glom())
 
 
+def _km_case(expr):
+  """(points, forced X, first centres) in spx_kmeans_step's domain."""
+  pts = rng.rand((600, 64), 23, np.float32)
+  return pts, expr.from_numpy(pts).force(), pts[:6].astype(np.float64)
+
+
+def _km_handoff_empty(p):
+  """No fused-step sums / counts, reduced counts, staged copies or queued step."""
+  return all(v is None for v in (p.step_X, p.step_labels, p.step_sums, p.step_counts, p.red_counts,
+                                 p.early_sums, p.early_counts, p.queued))
+
+
+def test_kmeans_api_nothing_outlives_the_fit(host_ctx):
+  """KMeans.fit leaves the joins' hand-off empty, and once the caller drops X
+  and the labels (and the eval / plan caches) both are freed: the state the
+  joins share refers to them weakly only."""
+  host_ctx(1)
+  import gc
+  import weakref
+  from spartan_amd import expr
+  from spartan_amd.examples import kmeans as km
+  from spartan_amd.expr import plan_cache
+  from spartan_amd.expr.base import eval_cache
+  pts, X, c0 = _km_case(expr)
+  c, labels = km.KMeans(6, 3).fit(X, c0)
+  assert _km_handoff_empty(km._PIPE) and not km._PIPE.following
+  lab_arr = labels.force()
+  assert lab_arr is labels.force()  # the array the joins were handed, not a new evaluation
+  wx, wl = weakref.ref(X), weakref.ref(lab_arr)
+  del X, labels, lab_arr
+  eval_cache.clear()
+  plan_cache.clear()
+  gc.collect()
+  assert wx() is None and wl() is None
+
+
+def test_kmeans_api_failed_fit_leaves_nothing(host_ctx):
+  """A fit that raises between the fused assignment and the joins leaves no
+  hand-off behind and the 'another iteration follows' flag down; the next
+  fit on the same X is bit-identical to one made before the failure."""
+  host_ctx(1)
+  from spartan_amd import backend, expr
+  from spartan_amd.examples import kmeans as km
+  pts, X, c0 = _km_case(expr)
+  c1, l1 = km.KMeans(6, 3).fit(X, c0)
+  l1 = l1.glom()
+  be = backend.get()
+  orig = be.kmeans_step
+  n = [0]
+
+  def failing(*a, **k):
+    n[0] += 1
+    if n[0] == 2:
+      raise RuntimeError('kmeans_step: injected failure')
+    return orig(*a, **k)
+  be.kmeans_step = failing
+  try:
+    with pytest.raises(RuntimeError, match='injected'):
+      km.KMeans(6, 3).fit(X, c0)
+  finally:
+    be.kmeans_step = orig
+  assert n[0] == 2
+  assert not km._PIPE.following and _km_handoff_empty(km._PIPE)
+  c2, l2 = km.KMeans(6, 3).fit(X, c0)
+  assert np.array_equal(c1.view(np.int64), c2.view(np.int64))
+  np.testing.assert_array_equal(l1, l2.glom())
+
+
+def test_kmeans_api_hand_written_loop_is_one_pass(host_ctx):
+  """outer / argmin / the two map2s written by hand, without KMeans.fit: the
+  count and centre joins still take the fused step's counts and sums (one
+  pass over X), and they equal the two-pass joins'."""
+  host_ctx(1)
+  from spartan_amd import backend, expr
+  from spartan_amd.examples import kmeans as km
+  pts, X, c0 = _km_case(expr)
+  be = backend.get()
+  calls = {'kmeans_step': 0, 'kmeans_accumulate': 0, 'bincount': 0}
+  origs = {n: getattr(be, n) for n in calls}
+
+  def counted(n):
+    def f(*a, **k):
+      calls[n] += 1
+      return origs[n](*a, **k)
+    return f
+
+  def one_iteration():
+    labels = expr.argmin(expr.outer((X, expr.from_numpy(c0)), (0, 0), fn=km.kmeans_dist_mapper, shape=(600, 6)),
+                         axis=1)
+    lab = labels.optimized().glom()
+    counts = expr.map2(labels, 0, fn=km.kmeans_count_mapper, fn_kw={'centers_count': 6}, shape=(6,))
+    sums = expr.map2((X, labels), (0, 0), fn=km.kmeans_center_mapper, fn_kw={'centers_count': 6}, shape=(6, 64))
+    return lab, counts.optimized().glom(), sums.optimized().glom()
+  for n in calls:
+    setattr(be, n, counted(n))
+  try:
+    l1, n1, s1 = one_iteration()
+    fused = dict(calls)
+    dom = km._step_domain
+    km._step_domain = lambda X, K: False
+    try:
+      l2, n2, s2 = one_iteration()
+    finally:
+      km._step_domain = dom
+  finally:
+    for n, f in origs.items():
+      setattr(be, n, f)
+  # (the test double's kmeans_step makes one kmeans_accumulate call itself)
+  assert fused == {'kmeans_step': 1, 'kmeans_accumulate': 1, 'bincount': 0}
+  assert calls['kmeans_step'] == 1 and calls['bincount'] == 1 and calls['kmeans_accumulate'] == 2
+  np.testing.assert_array_equal(l1, l2)
+  np.testing.assert_array_equal(n1, n2)
+  assert np.array_equal(s1.view(np.int32), s2.view(np.int32)) and n1.sum() == 600
+
+
+def test_kmeans_row_cache_is_by_tile_identity(host_ctx):
+  """_row_blocks keeps X's row blocks while every local tile tensor is the
+  same object; a replaced tile tensor is gathered again."""
+  host_ctx(1)
+  from spartan_amd import expr
+  from spartan_amd.examples import kmeans as km
+  pts, X, c0 = _km_case(expr)
+  blocks, got = km._row_blocks(X, 64)
+  again = km._row_blocks(X, 64)
+  assert again[0] is blocks and again[1] is got
+  tile = next(iter(X.local.values()))
+  old = tile.data
+  tile.data = old.clone()
+  blocks2, got2 = km._row_blocks(X, 64)
+  assert blocks2 is not blocks and got2 is not got
+  now = {t.data.untyped_storage().data_ptr() for t in X.local.values()}
+  assert old.untyped_storage().data_ptr() not in now
+  assert all(r.untyped_storage().data_ptr() in now for r in got2.values())
+  np.testing.assert_array_equal(np.concatenate([got2[i].numpy() for i in sorted(got2)]), pts)
+  assert km._row_blocks(X, 64)[0] is blocks2
+
+
 def _host_mapper_cases(expr):
   """(name, expression, NumPy result) for mappers that cannot be traced into
   a kernel -- data-dependent control flow, non-ufunc NumPy calls on the tile
@@ -561,3 +698,35 @@ def test_upload_alias_bitwise_and_one_shot():
   assert transfer._take_alias(host.reshape(4), cpu) is None         # shape differs
   transfer.register_upload_alias(host, dev, _Ev())
   assert transfer._take_alias(host.astype(np.float32), cpu) is None  # dtype differs
+
+
+def test_shadow_and_alias_withdrawal():
+  """array/transfer.py drop_shadow / drop_upload_alias: a producer about to
+  reuse its host copy withdraws the entry; a withdrawn shadow is not served by
+  download nor a withdrawn alias by upload; dropping for another tensor
+  leaves the entry in place."""
+  import torch
+  from spartan_amd.array import transfer
+  t = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+  u = torch.zeros((2, 3), dtype=torch.float64)
+  host = np.full((2, 3), 7.0)
+  n0 = _Ev.n
+  transfer.attach_shadow(t, host, _Ev())
+  transfer.drop_shadow(u)                                           # another tensor: stays
+  np.testing.assert_array_equal(transfer.download(t), host)
+  assert _Ev.n == n0 + 1
+  transfer.attach_shadow(t, host, _Ev())
+  transfer.drop_shadow(t)
+  assert not transfer._SHADOWS
+  np.testing.assert_array_equal(transfer.download(t), t.numpy())   # not served
+  assert _Ev.n == n0 + 1
+  cpu = torch.device('cpu')
+  transfer.register_upload_alias(t.numpy().copy(), t, _Ev())
+  transfer.drop_upload_alias(u)                                     # another tensor: stays
+  assert transfer._take_alias(t.numpy().copy(), cpu) is t
+  transfer.register_upload_alias(t.numpy().copy(), t, _Ev())
+  transfer.drop_upload_alias(t)
+  assert not transfer._ALIAS
+  up = transfer.upload(t.numpy().copy(), cpu)
+  assert up is not t and _Ev.n == n0 + 2
+  np.testing.assert_array_equal(up.numpy(), t.numpy())
