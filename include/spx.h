@@ -35,7 +35,7 @@ extern "C" {
  * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
- * spx_csrmm, spx_csr_todense */
+ * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj */
 
 /* error codes */
 #define SPX_OK 0
@@ -538,6 +538,46 @@ int spx_geqr(int dtype, int64_t m, int64_t n, const void* A, int64_t lda, void* 
              size_t workspace_bytes, void* stream);
 int spx_orgqr(int dtype, int64_t m, int64_t n, void* workspace, size_t workspace_bytes, const void* C, int64_t ldc,
               void* Q, int64_t ldq, void* stream);
+
+/* ------------------------------------------- symmetric eigen-solver (Jacobi)
+ * All eigenvalues and eigenvectors of `batch` symmetric n x n matrices, what
+ * np.linalg.eigh computes for an (..., n, n) array, by the parallel cyclic
+ * Jacobi method: one workgroup per matrix, which never leaves LDS, the grid
+ * over the batch.  float32 and float64 only (another dtype: SPX_ENOTSUP);
+ * asynchronous on the stream; no workspace.
+ *
+ * The plan call returns SPX_OK and writes the size limit *nmax of the dtype
+ * (128 for float32, 96 for float64: A and V, n columns of n + 1 each, and the
+ * round's table fit the 160 KiB one workgroup may declare) and *sweep_max (64);
+ * either pointer may be NULL.
+ *
+ * Matrix b is A + b stride_a, row-major with leading dimension lda >= n; only
+ * the triangle named by uplo (0: 'L', 1: 'U') is read -- the other one may hold
+ * anything, NaN included -- and A is never written.  W + b stride_w receives the
+ * n eigenvalues in ascending order, V + b stride_v (n x n, leading dimension
+ * ldv) the eigenvectors as columns in the same order, each with its entry of
+ * largest magnitude (the first on a tie) positive.  info[b] is the number of
+ * sweeps used (>= 0; 0 for the zero matrix and for n = 1), or -1 when matrix b
+ * did not converge within sweep_max sweeps or its triangle holds a non-finite
+ * value: W and V of that matrix are then filled with NaN and the other
+ * matrices of the batch are not affected.  Bytes beyond column n of any row of
+ * A and V, and beyond entry n of W, are neither read nor written.
+ *
+ * The matrix is scaled by the power of two of its largest magnitude (exact);
+ * a pair is rotated while |a_pq| > u ||A||_F / n (u the unit roundoff), so that
+ * off(A)_F < u ||A||_F at convergence; a sweep is the m - 1 rounds of a
+ * round-robin ordering over m = n + (n & 1) indices.  The workgroup size
+ * depends on n alone and there are no atomics: a matrix gives the same bits
+ * wherever it stands in a batch and whatever the batch size.
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a null pointer,
+ * a negative size, an uplo other than 0 / 1, a leading dimension below n, a
+ * negative stride_a or (batch > 1) output strides that let two matrices
+ * overlap; SPX_ENOTSUP for n > nmax or batch >= 2^31; batch == 0 or n == 0 is
+ * SPX_OK with no launch.  Additive since ABI 3. */
+int spx_syevj_plan(int dtype, int64_t* nmax, int64_t* sweep_max);
+int spx_syevj(int dtype, int uplo, int64_t batch, int64_t n, const void* A, int64_t lda, int64_t stride_a, void* W,
+              int64_t stride_w, void* V, int64_t ldv, int64_t stride_v, int32_t* info, void* stream);
 
 /* ------------------------------------------------- sparse (CSR) x dense
  * Replaces the scipy.sparse branches of the reference's dot

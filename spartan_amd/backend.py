@@ -167,6 +167,10 @@ _SIGS = {
                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
     'spx_orgqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
+    'spx_syevj_plan': ([ctypes.c_int, _I64P, _I64P], ctypes.c_int),
+    'spx_syevj': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                   ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     'spx_csrmm_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P, _I64P],
                        ctypes.c_int),
     'spx_csrmm_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
@@ -370,6 +374,17 @@ def geqr_plan(dtype, n):
     raise ValueError('geqr_plan: negative n = %d' % n)
   v = [ctypes.c_int64(0) for _ in range(2)]
   _check(load_library().spx_geqr_plan(spx_dtype(dt), int(n), *[ctypes.byref(x) for x in v]), 'spx_geqr_plan')
+  return tuple(int(x.value) for x in v)
+
+
+def syevj_plan(dtype):
+  """(nmax, sweep_max) of spx_syevj for ``dtype``, from the library: the
+  largest n one workgroup holds in LDS and the bound on the sweeps."""
+  dt = np.dtype(dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise TypeError('syevj_plan: dtype %s has no eigen-solver kernel (float32 / float64)' % dt)
+  v = [ctypes.c_int64(0) for _ in range(2)]
+  _check(load_library().spx_syevj_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_syevj_plan')
   return tuple(int(x.value) for x in v)
 
 
@@ -1512,6 +1527,48 @@ class HipBackend:
                               ctypes.c_void_p(Q.data_ptr()), ldq, self.stream()), 'spx_orgqr')
     if ev is not None:
       ev[1].record()
+
+  # ------------------------------------------------------------------ eigh
+  def syevj(self, A, uplo='L'):
+    """(W, V, info) of the symmetric ``A``, (n, n) or a batch (B, n, n)
+    (spx_syevj): W (n,) / (B, n) the ascending eigenvalues, V of A's shape the
+    eigenvectors as columns, ``info`` the int32 device tensor (one entry per
+    matrix) of the sweeps used, -1 where a matrix did not converge or is not
+    finite (its W and V are NaN); nothing here reads it.  Only the triangle
+    ``uplo`` names is read; ``A`` needs unit stride on its last axis and a row
+    stride of at least n, any batch stride, and is not written.  Asynchronous
+    on the current stream."""
+    import torch
+    if uplo not in ('L', 'U'):
+      raise ValueError("syevj: uplo must be 'L' or 'U', not %r" % (uplo,))
+    if A.dim() not in (2, 3):
+      raise ValueError('syevj: A must be 2-d or 3-d, got shape %s' % (tuple(A.shape),))
+    dt = np_dtype(A.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('syevj: A must be float32 / float64, not %s' % dt)
+    n = int(A.shape[-1])
+    if int(A.shape[-2]) != n:
+      raise ValueError('syevj: square matrices are needed, got shape %s' % (tuple(A.shape),))
+    nmax, _ = syevj_plan(dt)
+    if n > nmax:
+      raise ValueError('syevj: n = %d is above the limit %d for %s' % (n, nmax, dt))
+    batch = int(A.shape[0]) if A.dim() == 3 else 1
+    if batch > 0 and n > 1 and (A.stride(-1) != 1 or A.stride(-2) < n):
+      raise ValueError('syevj: A needs unit stride on its last axis and a row stride of at least %d' % n)
+    lda = int(A.stride(-2)) if n > 1 else max(n, 1)
+    stride_a = int(A.stride(0)) if A.dim() == 3 and batch > 1 else 0
+    W = torch.empty(tuple(A.shape[:-1]), dtype=A.dtype, device=A.device)
+    V = torch.empty(tuple(A.shape), dtype=A.dtype, device=A.device)
+    info = torch.zeros((batch,), dtype=torch.int32, device=A.device)
+    if batch == 0 or n == 0:
+      return W, V, info
+    ev = self._aot_events('spx_syevj')
+    _check(self.lib.spx_syevj(spx_dtype(dt), 0 if uplo == 'L' else 1, batch, n, ctypes.c_void_p(A.data_ptr()), lda,
+                              stride_a, ctypes.c_void_p(W.data_ptr()), n, ctypes.c_void_p(V.data_ptr()), n, n * n,
+                              ctypes.c_void_p(info.data_ptr()), self.stream()), 'spx_syevj')
+    if ev is not None:
+      ev[1].record()
+    return W, V, info
 
   # --------------------------------------------------------------- sparse
   @staticmethod

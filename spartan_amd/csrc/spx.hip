@@ -784,6 +784,9 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
 // ================================================= Householder TSQR (qr)
 #include "qr_kernels.h"
 
+// ===================================== batched Jacobi eigen-solver (eigh)
+#include "eigh_kernels.h"
+
 // ============================================== sparse (CSR) x dense, todense
 #include "sparse_kernels.h"
 

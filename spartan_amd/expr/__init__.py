@@ -7,6 +7,7 @@ from .builtins import (abs, add, arange, argmax, argmin, astype, bincount, conca
                        ln, log, maximum, max, mean, min, minimum, multiply, norm, ones, power, rand, randn,
                        size, sqrt, square, std, sub, sum, zeros)
 from .dot import dot
+from .eigh import eigh, eigvalsh
 from .filter import compress, take
 from .join import map2, outer
 from .linalg import cho_solve, cholesky, solve_triangular
