@@ -1,8 +1,11 @@
-"""Kernel backend: libspx.so (C ABI, include/spx.h) + generated-kernel JIT.
+"""Kernel backend: the device side of libspx.so + the generated-kernel JIT.
 
-This is the only module that touches the GPU compute path.  It loads the
-in-tree ``libspx.so`` (built by ``__graft_entry__.build()`` with hipcc for
-gfx950) and fails loudly if it is missing -- there is no CPU fallback.  Tests
+This is the only module that touches the GPU compute path: the JIT that
+compiles generated kernels for gfx950, the reduce planner and ``HipBackend``,
+which launches libspx.so's ahead-of-time kernels and the generated ones.  The
+binding itself -- the ctypes signature table, ``load_library``, the dtype
+codes and the plan / limit queries that need no GPU -- lives in ``binding``;
+its public names are re-exported here, so ``backend.X`` keeps working.  Tests
 may install a different backend object with ``set_backend`` to exercise the
 host logic without a GPU; product code never does.
 
@@ -19,373 +22,24 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import codegen
+from . import binding, codegen
 from .config import FLAGS
 from .layout import broadcast_strides, coalesce, reduce_view, contiguous_strides
+from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP_CODE, FILL_CONST, FILL_ARANGE,
+                     FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
+                     np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
+                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, current_stream,
+                     _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, 'libspx.so')
 SRC_PATH = os.path.join(_HERE, 'csrc', 'spx.hip')
 
-SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64 = 0, 1, 2, 3, 4
-OP_CODE = {'sum': 0, 'min': 1, 'max': 2, 'argmin': 3, 'argmax': 4, 'replace': 5}
-FILL_CONST, FILL_ARANGE, FILL_UNIFORM, FILL_NORMAL = 0, 1, 2, 3
 
-_DT = {np.dtype(np.bool_): SPX_BOOL, np.dtype(np.int32): SPX_I32, np.dtype(np.int64): SPX_I64,
-       np.dtype(np.float32): SPX_F32, np.dtype(np.float64): SPX_F64}
-
-
-def spx_dtype(dt):
-  dt = np.dtype(dt)
-  if dt not in _DT:
-    raise TypeError('dtype %s is not supported by the MI355X backend '
-                    '(bool, int32, int64, float32, float64)' % dt)
-  return _DT[dt]
-
-
-_TORCH_DT, _NP_DT = {}, {}  # NumPy dtype <-> torch dtype, filled on first use (torch is imported lazily)
-
-
-def _dtype_tables():
-  import torch
-  pairs = [(np.dtype(name), getattr(torch, name)) for name in ('bool', 'int32', 'int64', 'float32', 'float64')]
-  _NP_DT.update((t, d) for d, t in pairs)
-  _TORCH_DT.update(pairs)
-
-
-def torch_dtype(dt):
-  _TORCH_DT or _dtype_tables()
-  return _TORCH_DT[np.dtype(dt)]
-
-
-def np_dtype(tdt):
-  _NP_DT or _dtype_tables()
-  return _NP_DT[tdt]
-
-
-# ------------------------------------------------------------------ library
-_lib = None
-_lib_lock = threading.Lock()
-
-_I64P = ctypes.POINTER(ctypes.c_int64)
-_SIGS = {
-    'spx_abi_version': ([], ctypes.c_int),
-    'spx_last_error': ([], ctypes.c_char_p),
-    'spx_module_load': ([ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
-    'spx_module_unload': ([ctypes.c_void_p], ctypes.c_int),
-    'spx_module_function': ([ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
-    'spx_launch': ([ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_fill': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _I64P, _I64P, _I64P,
-                  ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p], ctypes.c_int),
-    'spx_reduce_finalize': ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                             ctypes.c_void_p], ctypes.c_int),
-    'spx_merge': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, _I64P, _I64P,
-                   _I64P, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    'spx_copy_region': ([ctypes.c_int, ctypes.c_void_p, _I64P, _I64P, ctypes.c_int, ctypes.c_void_p, _I64P,
-                         _I64P, ctypes.c_int, _I64P, ctypes.c_void_p], ctypes.c_int),
-    'spx_gemm': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                  ctypes.c_double, ctypes.c_double, ctypes.c_void_p], ctypes.c_int),
-    'spx_argreduce_combine': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
-    'spx_kmeans_assign_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64],
-                                     ctypes.c_int64),
-    'spx_kmeans_assign': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                           ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    'spx_kmeans_accumulate_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64],
-                                         ctypes.c_int64),
-    'spx_kmeans_accumulate': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_kmeans_step_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
-    'spx_kmeans_step': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                         ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    'spx_kmeans_timing': ([ctypes.c_int], ctypes.c_int),
-    'spx_kmeans_times': ([ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int],
-                         ctypes.c_int),
-    'spx_cdist': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
-    'spx_bincount': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                      ctypes.c_void_p], ctypes.c_int),
-    'spx_scan_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
-    'spx_scan': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                  ctypes.c_void_p], ctypes.c_int),
-    'spx_sort_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int],
-                           ctypes.c_int64),
-    'spx_sort': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_sort_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
-    'spx_topk_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                            ctypes.c_int], ctypes.c_int64),
-    'spx_topk': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                  ctypes.c_void_p], ctypes.c_int),
-    'spx_topk_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P],
-                      ctypes.c_int),
-    'spx_knn_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64],
-                          ctypes.c_int64),
-    'spx_knn': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                 ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_knn_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P],
-                     ctypes.c_int),
-    'spx_take': ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
-    'spx_compact_workspace': ([ctypes.c_int64], ctypes.c_int64),
-    'spx_compact_count': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                           ctypes.c_void_p], ctypes.c_int),
-    'spx_compact': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                     ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
-                    ctypes.c_int),
-    'spx_stencil_plan': ([ctypes.c_int, _I64P, _I64P, _I64P], ctypes.c_int),
-    'spx_stencil': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
-                    ctypes.c_int),
-    'spx_maxpool': ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                     ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
-    'spx_potrf_plan': ([ctypes.c_int, _I64P, _I64P], ctypes.c_int),
-    'spx_potrf_workspace': ([ctypes.c_int, ctypes.c_int64], ctypes.c_int64),
-    'spx_potrf': ([ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_trsm_workspace': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
-    'spx_trsm': ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
-                 ctypes.c_int),
-    'spx_syrk': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
-                 ctypes.c_int),
-    'spx_geqr_plan': ([ctypes.c_int, ctypes.c_int64, _I64P, _I64P], ctypes.c_int),
-    'spx_geqr_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
-    'spx_geqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
-    'spx_orgqr': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
-    'spx_syevj_plan': ([ctypes.c_int, _I64P, _I64P], ctypes.c_int),
-    'spx_syevj': ([ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                   ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
-    'spx_csrmm_plan': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _I64P, _I64P, _I64P],
-                       ctypes.c_int),
-    'spx_csrmm_workspace': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
-    'spx_csrmm': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                   ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
-                   ctypes.c_void_p], ctypes.c_int),
-    'spx_csr_todense': ([ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
-                        ctypes.c_int),
-    'spx_comm_load':([ctypes.c_char_p], ctypes.c_int),
-    'spx_comm_unique_id': ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
-    'spx_comm_init': ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)],
-                      ctypes.c_int),
-    'spx_comm_destroy': ([ctypes.c_void_p], ctypes.c_int),
-    'spx_allreduce': ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p], ctypes.c_int),
-    'spx_reduce_scatter': ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-                            ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    'spx_allgather': ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-                       ctypes.c_void_p], ctypes.c_int),
-    'spx_broadcast': ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p], ctypes.c_int),
-    'spx_reduce': ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                    ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    'spx_sendrecv': ([ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), _I64P,
-                      ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), _I64P,
-                      ctypes.POINTER(ctypes.c_int), ctypes.c_void_p], ctypes.c_int),
-    'spx_mincost_tiling': ([ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
-                            ctypes.POINTER(ctypes.c_int32), _I64P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
-                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), _I64P], ctypes.c_int),
-}
-EXPORTED = tuple(_SIGS)
-
-
-def load_library(path=LIB_PATH):
-  """Load libspx.so (importing torch first so its HIP runtime is the one used)."""
-  global _lib
-  with _lib_lock:
-    if _lib is not None:
-      return _lib
-    import torch  # noqa: F401  (torch's libamdhip64.so.7 must be the loaded runtime)
-    if not os.path.exists(path):
-      raise RuntimeError('libspx.so not found at %s: run __graft_entry__.build() '
-                         '(hipcc --offload-arch=gfx950); there is no CPU fallback' % path)
-    lib = ctypes.CDLL(path)
-    for name, (args, res) in _SIGS.items():
-      fn = getattr(lib, name)
-      fn.argtypes = args
-      fn.restype = res
-    _lib = lib
-    return lib
-
-
-def mincost_tiling(t, edges, split_pairs):
-  """spx_mincost_tiling (host code in libspx.so, no GPU needed): the node
-  choice of the AutomaticTiling cost graph.  edges: [(u, v, cost)] in
-  insertion order; split_pairs: [(a, b)].  Returns (chosen node ids < t,
-  total cost)."""
-  lib = load_library()
-  n = len(edges)
-  I32 = ctypes.c_int32
-  eu = (I32 * max(n, 1))(*[int(e[0]) for e in edges])
-  ev = (I32 * max(n, 1))(*[int(e[1]) for e in edges])
-  ec = (ctypes.c_int64 * max(n, 1))(*[int(e[2]) for e in edges])
-  m = len(split_pairs)
-  su = (I32 * max(m, 1))(*[int(p[0]) for p in split_pairs])
-  sv = (I32 * max(m, 1))(*[int(p[1]) for p in split_pairs])
-  chosen = (ctypes.c_uint8 * max(int(t), 1))()
-  total = ctypes.c_int64(0)
-  rc = lib.spx_mincost_tiling(int(t), n, eu, ev, ec, m, su, sv, chosen, ctypes.byref(total))
-  if rc != 0:
-    raise ValueError('spx_mincost_tiling: malformed tiling graph')
-  return [u for u in range(int(t)) if chosen[u]], int(total.value)
-
-
-SCAN_CHUNK = 32768  # elements of a line per chunk of a chunked scan (csrc/scan_kernels.h)
-
-
-def scan_dtypes(dt):
-  """(result dtype, accumulator dtype) of a cumulative sum over ``dt``:
-  np.cumsum's result dtype; carries and totals are int64 / float64."""
-  dt = np.dtype(dt)
-  spx_dtype(dt)
-  if dt.kind == 'f':
-    return dt, np.dtype(np.float64)
-  return np.dtype(np.int64), np.dtype(np.int64)
-
-
-def scan_plan(outer, n, inner, dtype):
-  """(mode, chunk) spx_scan uses for an (outer, n, inner) scan of ``dtype``:
-  'line' (one pass, a workgroup or wave walks whole lines; chunk == n) or
-  'chunked' (lines cut into SCAN_CHUNK elements over three launches).  The
-  library decides from the geometry and the CU count; a chunked scan is the
-  one that needs a workspace."""
-  need = load_library().spx_scan_workspace(spx_dtype(dtype), int(outer), int(n), int(inner))
-  if need < 0:
-    raise ValueError('scan_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
-  return ('chunked', SCAN_CHUNK) if need > 0 else ('line', int(n))
-
-
-SORT_LDS_MAX = 2048  # longest line spx_sort sorts in LDS (csrc/sort_kernels.h)
-SORT_TILE = 16384    # keys per workgroup and radix pass (csrc/sort_kernels.h)
-
-
-def sort_plan(outer, n, inner, dtype, want_idx=False):
-  """(path, passes) spx_sort uses for an (outer, n, inner) sort of ``dtype``:
-  ('lds', 0) -- lines of at most SORT_LDS_MAX keys, sorted in LDS, no
-  workspace -- or ('radix', passes), least-significant-digit passes over
-  tiles of SORT_TILE keys.  The library's own answer (spx_sort_plan);
-  ``want_idx`` changes the workspace, not the path."""
-  rc = load_library().spx_sort_plan(spx_dtype(dtype), int(outer), int(n), int(inner), None, None)
-  if rc < 0:
-    raise ValueError('sort_plan: bad geometry (%s, %s, %s)' % (outer, n, inner))
-  return ('radix', rc) if rc > 0 else ('lds', 0)
-
-
-def topk_plan(outer, n, inner, dtype, k=1):
-  """(path, passes, chunk) spx_topk uses for an (outer, n, inner) selection
-  of ``dtype``: ('lds', 0, chunk) -- lines of at most SORT_LDS_MAX elements,
-  sorted in LDS -- or ('select', passes, chunk), most-significant-digit radix
-  select passes over chunks of ``chunk`` elements (spx_topk_plan)."""
-  chunk = ctypes.c_int64(0)
-  rc = load_library().spx_topk_plan(spx_dtype(dtype), int(outer), int(n), int(inner), int(k), None,
-                                    ctypes.byref(chunk))
-  if rc < 0:
-    raise ValueError('topk_plan: bad geometry (%s, %s, %s), k %s' % (outer, n, inner, k))
-  return ('select', rc, int(chunk.value)) if rc > 0 else ('lds', 0, int(chunk.value))
-
-
-def knn_plan(Q, N, D, k, dtype=np.float32):
-  """(number of point ranges, range length) of spx_knn (spx_knn_plan)."""
-  chunk = ctypes.c_int64(0)
-  rc = load_library().spx_knn_plan(spx_dtype(dtype), int(Q), int(N), int(D), int(k), None, ctypes.byref(chunk))
-  if rc < 0:
-    raise ValueError('knn_plan: bad arguments (Q %s, N %s, D %s, k %s)' % (Q, N, D, k))
-  return rc, int(chunk.value)
-
-
-def _k_limit(which):
-  """TOPK_K_MAX / KNN_K_MAX: the library's own limits, through the plan calls."""
-  if which in globals():
-    return globals()[which]
-  kmax = ctypes.c_int64(0)
-  lib = load_library()
-  if which == 'TOPK_K_MAX':
-    lib.spx_topk_plan(SPX_F32, 1, 1, 1, 1, ctypes.byref(kmax), None)
-  else:
-    lib.spx_knn_plan(SPX_F32, 1, 1, 1, 1, ctypes.byref(kmax), None)
-  globals()[which] = int(kmax.value)
-  return int(kmax.value)
-
-
-def compact_tile():
-  """Mask bytes per workgroup of spx_compact_count / spx_compact
-  (COMPACT_TILE in csrc/index_kernels.h), read from the library: the
-  workspace starts with one int64 per tile, so the tile is the longest mask
-  whose workspace is a single entry.  Also ``backend.COMPACT_TILE``."""
-  ws = load_library().spx_compact_workspace
-  lo, hi = 1, 1 << 40  # ws(lo) == 8 < ws(hi)
-  while hi - lo > 1:
-    mid = (lo + hi) // 2
-    if ws(mid) <= 8:
-      lo = mid
-    else:
-      hi = mid
-  return lo
-
-
-def stencil_plan(dtype):
-  """(bm, bn, bk): the block tile of spx_stencil for ``dtype`` (float32 /
-  float64) -- rows of F, columns of W * H and the K-tile of C * fw * fh
-  (StencilTile in csrc/stencil_kernels.h), read from the library."""
-  dt = np.dtype(dtype)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('stencil_plan: dtype %s has no stencil kernel (float32 / float64)' % dt)
-  v = [ctypes.c_int64(0) for _ in range(3)]
-  _check(load_library().spx_stencil_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_stencil_plan')
-  return tuple(int(x.value) for x in v)
-
-
-def potrf_plan(dtype):
-  """(nb, nb_outer): the diagonal block one workgroup factors in LDS and the
-  outer panel (the K of the trailing update) of spx_potrf, from the library."""
-  dt = np.dtype(dtype)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('potrf_plan: dtype %s has no Cholesky kernel (float32 / float64)' % dt)
-  v = [ctypes.c_int64(0) for _ in range(2)]
-  _check(load_library().spx_potrf_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_potrf_plan')
-  return tuple(int(x.value) for x in v)
-
-
-def geqr_plan(dtype, n):
-  """(nmax, r) of spx_geqr for ``n`` columns of ``dtype``, from the library:
-  the column limit and the rows one workgroup factors in LDS (r >= 2 n; 0 where
-  n is above the limit)."""
-  dt = np.dtype(dtype)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('geqr_plan: dtype %s has no QR kernel (float32 / float64)' % dt)
-  if int(n) < 0:
-    raise ValueError('geqr_plan: negative n = %d' % n)
-  v = [ctypes.c_int64(0) for _ in range(2)]
-  _check(load_library().spx_geqr_plan(spx_dtype(dt), int(n), *[ctypes.byref(x) for x in v]), 'spx_geqr_plan')
-  return tuple(int(x.value) for x in v)
-
-
-def syevj_plan(dtype):
-  """(nmax, sweep_max) of spx_syevj for ``dtype``, from the library: the
-  largest n one workgroup holds in LDS and the bound on the sweeps."""
-  dt = np.dtype(dtype)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('syevj_plan: dtype %s has no eigen-solver kernel (float32 / float64)' % dt)
-  v = [ctypes.c_int64(0) for _ in range(2)]
-  _check(load_library().spx_syevj_plan(spx_dtype(dt), *[ctypes.byref(x) for x in v]), 'spx_syevj_plan')
-  return tuple(int(x.value) for x in v)
+def __getattr__(name):
+  if name in ('COMPACT_TILE', 'TOPK_K_MAX', 'KNN_K_MAX'):  # read from the library on first use
+    return getattr(binding, name)
+  raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
 class QrHandle:
@@ -397,22 +51,6 @@ class QrHandle:
     self.workspace, self.m, self.n, self.dtype = workspace, m, n, dtype
 
 
-def csrmm_plan(dtype, m, nnz, p):
-  """(g, T, rows_per_block) of spx_csrmm for an (m, .) CSR matrix of ``nnz``
-  nonzeros times ``p`` dense columns, from the library: the lanes that work on
-  one row, the row length above which a row is cut into chunks of T for whole
-  workgroups, and the rows one workgroup covers."""
-  dt = np.dtype(dtype)
-  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-    raise TypeError('csrmm_plan: dtype %s has no sparse kernel (float32 / float64)' % dt)
-  if min(int(m), int(nnz), int(p)) < 0:
-    raise ValueError('csrmm_plan: negative size (%d, %d, %d)' % (m, nnz, p))
-  v = [ctypes.c_int64(0) for _ in range(3)]
-  _check(load_library().spx_csrmm_plan(spx_dtype(dt), int(m), int(nnz), int(p), *[ctypes.byref(x) for x in v]),
-         'spx_csrmm_plan')
-  return tuple(int(x.value) for x in v)
-
-
 class CsrWorkspace:
   """The cached structure analysis of one CSR tile for ``csrmm``: the workspace
   tensor and whether a call has left the long-row lists in it."""
@@ -420,25 +58,6 @@ class CsrWorkspace:
 
   def __init__(self):
     self.buf, self.prepared = None, False
-
-
-def __getattr__(name):
-  if name == 'COMPACT_TILE':
-    globals()['COMPACT_TILE'] = t = compact_tile()
-    return t
-  if name in ('TOPK_K_MAX', 'KNN_K_MAX'):
-    return _k_limit(name)
-  raise AttributeError('module %r has no attribute %r' % (__name__, name))
-
-
-def _arr(vals):
-  vals = [int(v) for v in vals] or [0]
-  return (ctypes.c_int64 * len(vals))(*vals)
-
-
-def _check(rc, what):
-  if rc != 0:
-    raise RuntimeError('%s failed (%d): %s' % (what, rc, _lib.spx_last_error().decode()))
 
 
 # ------------------------------------------------------------ JIT compile
@@ -670,11 +289,7 @@ class HipBackend:
 
   # ---------------------------------------------------------------- utils
   def stream(self):
-    # the raw pointer of the current stream, without building a torch Stream
-    # object (torch.cuda.current_stream() cost ~10 us per call, three calls
-    # per lreg iteration)
-    import torch
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+    return current_stream()
 
   def kernel(self, src, name):
     key = source_key(src)
@@ -702,13 +317,29 @@ class HipBackend:
     ev[0].record()
     return ev
 
-  def _aot_events(self, name):
-    """_events() around one ahead-of-time libspx call, logged under ``name``;
-    the caller records the end event."""
-    ev = self._events()
+  def _call(self, name, *args, timed=True):
+    """One ahead-of-time libspx call ``name`` on the current stream, which
+    every compute entry point takes last.  ``timed``: between _events(), logged
+    under ``name``.  The arguments go to ctypes as they are."""
+    ev = self._events() if timed else None
     if ev is not None:
       self.kernel_events.append((name, ev[0], ev[1]))
-    return ev
+    _check(getattr(self.lib, name)(*args, current_stream()), name)
+    if ev is not None:
+      ev[1].record()
+
+  def _workspace_for(self, query, sizes, device, bad, floor=0, exc=ValueError):
+    """(tensor or None, its bytes): the shared scratch buffer of at least
+    ``floor`` bytes that the library's ``query`` asks for ``sizes``; ``exc(bad)``
+    where it rejects them."""
+    need = getattr(self.lib, query)(*sizes)
+    if need < 0:
+      raise exc(bad)
+    need = max(int(need), floor)
+    if need == 0:
+      return None, 0
+    ws = self._workspace(need, device)
+    return ws, ws.numel()
 
   def kmeans_timing(self, enable):
     """Record HIP events around the one-pass kernel of every later fused
@@ -731,7 +362,7 @@ class HipBackend:
     args.grid = grid
     ev = self._events()
     _check(self.lib.spx_launch(fn, grid, 1, 1, 256, 0, ctypes.byref(args), ctypes.sizeof(args),
-                               self.stream()), 'spx_launch')
+                               current_stream()), 'spx_launch')
     if ev is not None:
       ev[1].record()
       self.kernel_events.append((self._names.get(fn.value, '?'), ev[0], ev[1]))
@@ -740,9 +371,8 @@ class HipBackend:
   def fill(self, out, kind, a, b, seed, ul, array_shape):
     shape = tuple(out.shape)
     nd = len(shape)
-    _check(self.lib.spx_fill(spx_dtype(np_dtype(out.dtype)), kind, ctypes.c_void_p(out.data_ptr()), nd,
-                             _arr(shape), _arr(ul), _arr(array_shape), float(a), float(b),
-                             int(seed) & 0xFFFFFFFFFFFFFFFF, self.stream()), 'spx_fill')
+    self._call('spx_fill', spx_dtype(np_dtype(out.dtype)), kind, _ptr(out), nd, _arr(shape), _arr(ul),
+               _arr(array_shape), float(a), float(b), int(seed) & 0xFFFFFFFFFFFFFFFF, timed=False)
 
   # ------------------------------------------------------------------ map
   def map(self, root, inputs, out):
@@ -919,8 +549,8 @@ class HipBackend:
     """spx_reduce_finalize: ``parts`` (dtype pdt; arg ops: values, with their
     indices ``parts_i``) -> ``out`` (dtype odt; arg ops: the indices, values
     to ``out_v``)."""
-    _check(self.lib.spx_reduce_finalize(OP_CODE[op], spx_dtype(pdt), spx_dtype(odt), _ptr(parts), _ptr(parts_i),
-                                        P, n, _ptr(out), _ptr(out_v), self.stream()), 'spx_reduce_finalize')
+    self._call('spx_reduce_finalize', OP_CODE[op], spx_dtype(pdt), spx_dtype(odt), _ptr(parts), _ptr(parts_i), P, n,
+               _ptr(out), _ptr(out_v), timed=False)
 
   def argcombine(self, op, vals, idx):
     """vals/idx: [R, n] -> (val[n], idx[n]) best-of-R with first-index ties."""
@@ -928,28 +558,22 @@ class HipBackend:
     R, n = vals.shape[0], vals.shape[1] if vals.dim() > 1 else 1
     out_i = torch.empty((n,), dtype=torch.int64, device=vals.device)
     out_v = torch.empty((n,), dtype=vals.dtype, device=vals.device)
-    _check(self.lib.spx_argreduce_combine(OP_CODE[op], spx_dtype(np_dtype(vals.dtype)),
-                                          ctypes.c_void_p(vals.data_ptr()), ctypes.c_void_p(idx.data_ptr()),
-                                          R, n, ctypes.c_void_p(out_v.data_ptr()),
-                                          ctypes.c_void_p(out_i.data_ptr()), self.stream()),
-           'spx_argreduce_combine')
+    self._call('spx_argreduce_combine', OP_CODE[op], spx_dtype(np_dtype(vals.dtype)), _ptr(vals), _ptr(idx), R, n,
+               _ptr(out_v), _ptr(out_i), timed=False)
     return out_v, out_i
 
   # ---------------------------------------------------------------- merge
   def merge(self, dst, mask, region_ul, src, op, fastpath=True):
     shape = tuple(dst.shape)
-    _check(self.lib.spx_merge(OP_CODE[op], spx_dtype(np_dtype(dst.dtype)), ctypes.c_void_p(dst.data_ptr()),
-                              ctypes.c_void_p(mask.data_ptr() if mask is not None else 0), len(shape),
-                              _arr(shape), _arr(region_ul), _arr(tuple(src.shape) if src.dim() else ()),
-                              ctypes.c_void_p(src.data_ptr()), spx_dtype(np_dtype(src.dtype)),
-                              1 if fastpath else 0, self.stream()), 'spx_merge')
+    self._call('spx_merge', OP_CODE[op], spx_dtype(np_dtype(dst.dtype)), _ptr(dst), _ptr(mask), len(shape),
+               _arr(shape), _arr(region_ul), _arr(tuple(src.shape) if src.dim() else ()), _ptr(src),
+               spx_dtype(np_dtype(src.dtype)), 1 if fastpath else 0, timed=False)
 
   def copy_region(self, dst, dst_ul, src, src_ul, shape):
     nd = len(shape)
-    _check(self.lib.spx_copy_region(spx_dtype(np_dtype(dst.dtype)), ctypes.c_void_p(dst.data_ptr()),
-                                    _arr(tuple(dst.shape)), _arr(dst_ul), spx_dtype(np_dtype(src.dtype)),
-                                    ctypes.c_void_p(src.data_ptr()), _arr(tuple(src.shape)), _arr(src_ul), nd,
-                                    _arr(shape), self.stream()), 'spx_copy_region')
+    self._call('spx_copy_region', spx_dtype(np_dtype(dst.dtype)), _ptr(dst), _arr(tuple(dst.shape)), _arr(dst_ul),
+               spx_dtype(np_dtype(src.dtype)), _ptr(src), _arr(tuple(src.shape)), _arr(src_ul), nd, _arr(shape),
+               timed=False)
 
   MATERIALISE_LIMIT = 2 << 30  # bytes of one materialised slab (non-coalescible reductions)
 
@@ -990,13 +614,8 @@ class HipBackend:
     K2, N = B.shape
     assert K == K2 and tuple(C.shape) == (M, N)
     dt = np_dtype(A.dtype)
-    ev = self._aot_events('spx_gemm')
-    _check(self.lib.spx_gemm(spx_dtype(dt), M, N, K, ctypes.c_void_p(A.data_ptr()), A.stride(0),
-                             ctypes.c_void_p(B.data_ptr()), B.stride(0), ctypes.c_void_p(C.data_ptr()),
-                             C.stride(0), float(alpha), float(beta), self.stream()), 'spx_gemm')
-    if ev is not None:
-      ev[1].record()
-
+    self._call('spx_gemm', spx_dtype(dt), M, N, K, _ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(C), C.stride(0),
+               float(alpha), float(beta))
 
   # --------------------------------------------------------------- k-means
   def kmeans_assign(self, points, centers, labels, mindist=None, exact_only=False, dist_dtype=np.float64):
@@ -1010,30 +629,19 @@ class HipBackend:
     dt = spx_dtype(np_dtype(points.dtype))
     ws, nws = None, 0
     if mindist is None and not exact_only and N > 0:
-      need = self.lib.spx_kmeans_assign_workspace(dt, N, D, K)
-      if need < 0:
-        raise RuntimeError('spx_kmeans_assign_workspace: bad arguments')
-      ws = self._workspace(int(need), points.device)
-      nws = ws.numel()
-    _check(self.lib.spx_kmeans_assign(dt, N, D, K, ctypes.c_void_p(points.data_ptr()), points.stride(0),
-                                      ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(labels.data_ptr()),
-                                      ctypes.c_void_p(mindist.data_ptr() if mindist is not None else 0),
-                                      ctypes.c_void_p(ws.data_ptr() if ws is not None else 0), nws,
-                                      spx_dtype(dist_dtype), self.stream()), 'spx_kmeans_assign')
+      ws, nws = self._workspace_for('spx_kmeans_assign_workspace', (dt, N, D, K), points.device,
+                                    'spx_kmeans_assign_workspace: bad arguments', exc=RuntimeError)
+    self._call('spx_kmeans_assign', dt, N, D, K, _ptr(points), points.stride(0), _ptr(centers), _ptr(labels),
+               _ptr(mindist), _ptr(ws), nws, spx_dtype(dist_dtype), timed=False)
 
   def kmeans_accumulate(self, points, labels, sums, counts, zero_first=True):
     N, D = points.shape
     K = sums.shape[0]
     dt = spx_dtype(np_dtype(points.dtype))
-    need = self.lib.spx_kmeans_accumulate_workspace(dt, N, D, K)
-    if need < 0:
-      raise RuntimeError('spx_kmeans_accumulate_workspace: bad arguments')
-    ws = self._workspace(max(int(need), 8), points.device)
-    _check(self.lib.spx_kmeans_accumulate(dt, N, D, K, ctypes.c_void_p(points.data_ptr()), points.stride(0),
-                                          ctypes.c_void_p(labels.data_ptr()), ctypes.c_void_p(sums.data_ptr()),
-                                          ctypes.c_void_p(counts.data_ptr()), 1 if zero_first else 0,
-                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), self.stream()),
-           'spx_kmeans_accumulate')
+    ws, nws = self._workspace_for('spx_kmeans_accumulate_workspace', (dt, N, D, K), points.device,
+                                  'spx_kmeans_accumulate_workspace: bad arguments', floor=8, exc=RuntimeError)
+    self._call('spx_kmeans_accumulate', dt, N, D, K, _ptr(points), points.stride(0), _ptr(labels), _ptr(sums),
+               _ptr(counts), 1 if zero_first else 0, _ptr(ws), nws, timed=False)
 
   def kmeans_step(self, points, centers, labels, sums, counts, zero_first=True, dist_dtype=np.float64):
     """kmeans_assign + kmeans_accumulate in one call (spx_kmeans_step): the
@@ -1043,15 +651,10 @@ class HipBackend:
     assert centers.dtype == self._f64() and tuple(centers.shape) == (K, D) and labels.shape[0] == N
     assert tuple(sums.shape) == (K, D) and counts.shape[0] == K and sums.is_contiguous() and counts.is_contiguous()
     dt = spx_dtype(np_dtype(points.dtype))
-    need = self.lib.spx_kmeans_step_workspace(dt, N, D, K)
-    if need < 0:
-      raise RuntimeError('spx_kmeans_step_workspace: bad arguments')
-    ws = self._workspace(max(int(need), 8), points.device)
-    _check(self.lib.spx_kmeans_step(dt, N, D, K, ctypes.c_void_p(points.data_ptr()), points.stride(0),
-                                    ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(labels.data_ptr()),
-                                    ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()),
-                                    1 if zero_first else 0, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                    spx_dtype(dist_dtype), self.stream()), 'spx_kmeans_step')
+    ws, nws = self._workspace_for('spx_kmeans_step_workspace', (dt, N, D, K), points.device,
+                                  'spx_kmeans_step_workspace: bad arguments', floor=8, exc=RuntimeError)
+    self._call('spx_kmeans_step', dt, N, D, K, _ptr(points), points.stride(0), _ptr(centers), _ptr(labels),
+               _ptr(sums), _ptr(counts), 1 if zero_first else 0, _ptr(ws), nws, spx_dtype(dist_dtype), timed=False)
 
   def cdist(self, points, centers, out):
     """out (N, K) = exact-order cdist(points, centers), rounded to out's dtype."""
@@ -1059,17 +662,14 @@ class HipBackend:
     K = centers.shape[0]
     assert centers.dtype == self._f64() and tuple(centers.shape) == (K, D) and tuple(out.shape) == (N, K)
     assert centers.is_contiguous() and points.stride(1) == 1 and out.stride(1) == 1
-    _check(self.lib.spx_cdist(spx_dtype(np_dtype(points.dtype)), spx_dtype(np_dtype(out.dtype)), N, D, K,
-                              ctypes.c_void_p(points.data_ptr()), points.stride(0),
-                              ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.stride(0),
-                              self.stream()), 'spx_cdist')
+    self._call('spx_cdist', spx_dtype(np_dtype(points.dtype)), spx_dtype(np_dtype(out.dtype)), N, D, K, _ptr(points),
+               points.stride(0), _ptr(centers), _ptr(out), out.stride(0), timed=False)
 
   def bincount(self, labels, counts, zero_first=True):
     """counts (K,) int64 (+)= bincount of int64 ``labels`` (out-of-range skipped)."""
     assert labels.dtype == counts.dtype and labels.is_contiguous() and counts.is_contiguous()
-    _check(self.lib.spx_bincount(ctypes.c_void_p(labels.data_ptr()), labels.numel(), counts.numel(),
-                                 ctypes.c_void_p(counts.data_ptr()), 1 if zero_first else 0, self.stream()),
-           'spx_bincount')
+    self._call('spx_bincount', _ptr(labels), labels.numel(), counts.numel(), _ptr(counts), 1 if zero_first else 0,
+               timed=False)
 
   # ----------------------------------------------------------------- scan
   def scan(self, src, out, axis_geom, carry=None, totals=None, exclusive=False):
@@ -1085,24 +685,15 @@ class HipBackend:
     odt, adt = scan_dtypes(dt)
     if not src.is_contiguous() or src.numel() != outer * n * inner:
       raise ValueError('scan: src must be contiguous with %d elements' % (outer * n * inner))
-    if out is not None and (np_dtype(out.dtype) != odt or not out.is_contiguous() or out.numel() != src.numel()):
-      raise ValueError('scan: out must be a contiguous %s tensor of src\'s size' % odt)
+    if out is not None:
+      _dense('scan: out', out, odt, src.numel(), 'src\'s size')
     for name, t in (('carry', carry), ('totals', totals)):
-      if t is not None and (np_dtype(t.dtype) != adt or not t.is_contiguous() or t.numel() != outer * inner):
-        raise ValueError('scan: %s must be a contiguous %s tensor of %d elements' % (name, adt, outer * inner))
-    need = self.lib.spx_scan_workspace(spx_dtype(dt), outer, n, inner)
-    if need < 0:
-      raise ValueError('scan: bad geometry %s' % (axis_geom,))
-    ws = self._workspace(int(need), src.device) if need > 0 else None
-    ev = self._aot_events('spx_scan')
-    _check(self.lib.spx_scan(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()),
-                             ctypes.c_void_p(out.data_ptr() if out is not None else 0), outer, n, inner,
-                             ctypes.c_void_p(carry.data_ptr() if carry is not None else 0),
-                             ctypes.c_void_p(totals.data_ptr() if totals is not None else 0),
-                             1 if exclusive else 0, ctypes.c_void_p(ws.data_ptr() if ws is not None else 0),
-                             ws.numel() if ws is not None else 0, self.stream()), 'spx_scan')
-    if ev is not None:
-      ev[1].record()
+      if t is not None:
+        _dense('scan: %s' % name, t, adt, outer * inner, '%d elements' % (outer * inner))
+    ws, nws = self._workspace_for('spx_scan_workspace', (spx_dtype(dt), outer, n, inner), src.device,
+                                  'scan: bad geometry %s' % (axis_geom,))
+    self._call('spx_scan', spx_dtype(dt), _ptr(src), _ptr(out), outer, n, inner, _ptr(carry), _ptr(totals),
+               1 if exclusive else 0, _ptr(ws), nws)
 
   # ----------------------------------------------------------------- sort
   def sort(self, src, out_vals, out_idx, axis_geom):
@@ -1121,22 +712,15 @@ class HipBackend:
     for name, t, odt in (('out_vals', out_vals, dt), ('out_idx', out_idx, np.dtype(np.int64))):
       if t is None:
         continue
-      if np_dtype(t.dtype) != odt or not t.is_contiguous() or t.numel() != src.numel():
-        raise ValueError('sort: %s must be a contiguous %s tensor of src\'s size' % (name, odt))
+      _dense('sort: %s' % name, t, odt, src.numel(), 'src\'s size')
       if src.numel() and t.data_ptr() == src.data_ptr():
         raise ValueError('sort: %s may not be src' % name)
-    need = self.lib.spx_sort_workspace(spx_dtype(dt), outer, n, inner, 1 if out_idx is not None else 0)
-    if need < 0:
-      raise ValueError('sort: bad geometry %s' % (axis_geom,))
+    ws, nws = self._workspace_for('spx_sort_workspace',
+                                  (spx_dtype(dt), outer, n, inner, 1 if out_idx is not None else 0), src.device,
+                                  'sort: bad geometry %s' % (axis_geom,))
     if src.numel() == 0:
       return
-    ws = self._workspace(int(need), src.device) if need > 0 else None
-    ev = self._aot_events('spx_sort')
-    _check(self.lib.spx_sort(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(out_vals), _ptr(out_idx),
-                             outer, n, inner, _ptr(ws), ws.numel() if ws is not None else 0, self.stream()),
-           'spx_sort')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_sort', spx_dtype(dt), _ptr(src), _ptr(out_vals), _ptr(out_idx), outer, n, inner, _ptr(ws), nws)
 
   # ----------------------------------------------------------------- topk
   def topk(self, src, in_idx, out_vals, out_idx, axis_geom, k, largest=False):
@@ -1159,28 +743,21 @@ class HipBackend:
       raise ValueError('topk: k %d is outside [1, %d]' % (k, n))
     if k > _k_limit('TOPK_K_MAX'):
       raise ValueError('topk: k %d exceeds TOPK_K_MAX = %d' % (k, _k_limit('TOPK_K_MAX')))
-    if in_idx is not None and (np_dtype(in_idx.dtype) != i64 or not in_idx.is_contiguous()
-                               or in_idx.numel() != src.numel()):
-      raise ValueError('topk: in_idx must be a contiguous int64 tensor of src\'s size')
+    if in_idx is not None:
+      _dense('topk: in_idx', in_idx, i64, src.numel(), 'src\'s size')
     for name, t, odt in (('out_vals', out_vals, dt), ('out_idx', out_idx, i64)):
       if t is None:
         continue
-      if np_dtype(t.dtype) != odt or not t.is_contiguous() or t.numel() != outer * k * inner:
-        raise ValueError('topk: %s must be a contiguous %s tensor of %d elements' % (name, odt, outer * k * inner))
+      _dense('topk: %s' % name, t, odt, outer * k * inner, '%d elements' % (outer * k * inner))
       if src.numel() and t.data_ptr() == src.data_ptr():
         raise ValueError('topk: %s may not be src' % name)
-    need = self.lib.spx_topk_workspace(spx_dtype(dt), outer, n, inner, k, 1 if out_idx is not None else 0)
-    if need < 0:
-      raise ValueError('topk: bad geometry %s, k %d' % (axis_geom, k))
+    ws, nws = self._workspace_for('spx_topk_workspace',
+                                  (spx_dtype(dt), outer, n, inner, k, 1 if out_idx is not None else 0), src.device,
+                                  'topk: bad geometry %s, k %d' % (axis_geom, k))
     if outer * inner == 0:
       return
-    ws = self._workspace(int(need), src.device) if need > 0 else None
-    ev = self._aot_events('spx_topk')
-    _check(self.lib.spx_topk(spx_dtype(dt), ctypes.c_void_p(src.data_ptr()), _ptr(in_idx), _ptr(out_vals),
-                             _ptr(out_idx), outer, n, inner, k, 1 if largest else 0, _ptr(ws),
-                             ws.numel() if ws is not None else 0, self.stream()), 'spx_topk')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_topk', spx_dtype(dt), _ptr(src), _ptr(in_idx), _ptr(out_vals), _ptr(out_idx), outer, n, inner, k,
+               1 if largest else 0, _ptr(ws), nws)
 
   def knn(self, points, queries, k, index_base, out_s, out_idx):
     """The k nearest of ``points`` (N, D) float32 / float64, unit column
@@ -1208,20 +785,13 @@ class HipBackend:
     for name, t, odt in (('out_s', out_s, np.dtype(np.float64)), ('out_idx', out_idx, np.dtype(np.int64))):
       if np_dtype(t.dtype) != odt or not t.is_contiguous() or tuple(t.shape) != (Q, k):
         raise ValueError('knn: %s must be a contiguous (%d, %d) %s tensor' % (name, Q, k, odt))
-    need = self.lib.spx_knn_workspace(spx_dtype(dt), Q, N, D, k)
-    if need < 0:
-      raise ValueError('knn: bad arguments (Q %d, N %d, D %d, k %d)' % (Q, N, D, k))
+    ws, nws = self._workspace_for('spx_knn_workspace', (spx_dtype(dt), Q, N, D, k), points.device,
+                                  'knn: bad arguments (Q %d, N %d, D %d, k %d)' % (Q, N, D, k), floor=8)
     if Q == 0:
       return
     ldp = int(points.stride(0)) if N > 1 else D
-    ws = self._workspace(max(int(need), 8), points.device)
-    ev = self._aot_events('spx_knn')
-    _check(self.lib.spx_knn(spx_dtype(dt), Q, N, D, k, ctypes.c_void_p(points.data_ptr()), ldp,
-                            ctypes.c_void_p(queries.data_ptr()), int(index_base), ctypes.c_void_p(out_s.data_ptr()),
-                            ctypes.c_void_p(out_idx.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                            self.stream()), 'spx_knn')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_knn', spx_dtype(dt), Q, N, D, k, _ptr(points), ldp, _ptr(queries), int(index_base), _ptr(out_s),
+               _ptr(out_idx), _ptr(ws), nws)
 
   # ------------------------------------------------------- take / compress
   def take(self, src, idx, out, geom, lo, n_total, out_strides=None):
@@ -1257,11 +827,8 @@ class HipBackend:
     if out.data_ptr() == src.data_ptr() and src.numel():
       raise ValueError('take: out may not be src')
     err = torch.empty((1,), dtype=torch.int32, device=src.device)
-    ev = self._aot_events('spx_take')
-    _check(self.lib.spx_take(spx_dtype(dt), spx_dtype(np_dtype(idx.dtype)), _ptr(src), _ptr(idx), _ptr(out), outer,
-                             n_total, lo, n_local, m, inner, oos, ors, _ptr(err), self.stream()), 'spx_take')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_take', spx_dtype(dt), spx_dtype(np_dtype(idx.dtype)), _ptr(src), _ptr(idx), _ptr(out), outer,
+               n_total, lo, n_local, m, inner, oos, ors, _ptr(err))
     if int(err.item()):
       raise IndexError('take: an index is out of bounds for an axis of length %d' % n_total)
 
@@ -1280,11 +847,7 @@ class HipBackend:
     if need < 0:
       raise ValueError('compact_count: bad length %d' % n)
     buf = torch.empty((need + 8,), dtype=torch.uint8, device=mask.device)  # the workspace and the total's word
-    ev = self._aot_events('spx_compact_count')
-    _check(self.lib.spx_compact_count(_ptr(mask), n, ctypes.c_void_p(buf.data_ptr() + need), _ptr(buf), need,
-                                      self.stream()), 'spx_compact_count')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_compact_count', _ptr(mask), n, _ptr(buf[need:]), _ptr(buf), need)
     return int(buf[need:].view(torch.int64).item()), buf[:need]
 
   def compact(self, src, mask, out, geom, workspace):
@@ -1316,11 +879,8 @@ class HipBackend:
       raise ValueError('compact: the workspace of compact_count(mask) is needed (%d bytes)' % need)
     if out.data_ptr() == src.data_ptr():
       raise ValueError('compact: out may not be src')
-    ev = self._aot_events('spx_compact')
-    _check(self.lib.spx_compact(spx_dtype(dt), _ptr(src), _ptr(mask), _ptr(out), outer, n, inner, count,
-                                _ptr(workspace), workspace.numel(), self.stream()), 'spx_compact')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_compact', spx_dtype(dt), _ptr(src), _ptr(mask), _ptr(out), outer, n, inner, count,
+               _ptr(workspace), workspace.numel())
 
   # ------------------------------------------------------ stencil / maxpool
   def stencil(self, images, filters, out):
@@ -1351,11 +911,7 @@ class HipBackend:
       return
     if out.data_ptr() in (images.data_ptr(), filters.data_ptr()):
       raise ValueError('stencil: out may not be an input')
-    ev = self._aot_events('spx_stencil')
-    _check(self.lib.spx_stencil(spx_dtype(dt), _ptr(images), _ptr(filters), _ptr(out), N, C, W, H, F, fw, fh,
-                                self.stream()), 'spx_stencil')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_stencil', spx_dtype(dt), _ptr(images), _ptr(filters), _ptr(out), N, C, W, H, F, fw, fh)
 
   def maxpool(self, src, out, pool_size, stride):
     """out[n, c, p, q] = max over i, j < pool_size with p stride + i < W and
@@ -1384,11 +940,7 @@ class HipBackend:
       return
     if out.data_ptr() == src.data_ptr():
       raise ValueError('maxpool: out may not be src')
-    ev = self._aot_events('spx_maxpool')
-    _check(self.lib.spx_maxpool(spx_dtype(dt), _ptr(src), _ptr(out), N * C, W, H, pool_size, stride, self.stream()),
-           'spx_maxpool')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_maxpool', spx_dtype(dt), _ptr(src), _ptr(out), N * C, W, H, pool_size, stride)
 
   # --------------------------------------------- cholesky / triangular solve
   @staticmethod
@@ -1424,18 +976,10 @@ class HipBackend:
     if n and L.data_ptr() == A.data_ptr() and lda != ldl:
       raise ValueError('potrf: in place needs the same row stride')
     info = torch.zeros((1,), dtype=torch.int32, device=A.device)
-    need = self.lib.spx_potrf_workspace(spx_dtype(dt), n)
-    if need < 0:
-      raise ValueError('potrf: bad size %d' % n)
+    ws, nws = self._workspace_for('spx_potrf_workspace', (spx_dtype(dt), n), A.device, 'potrf: bad size %d' % n)
     if n == 0:
       return info
-    ws = self._workspace(int(need), A.device) if need > 0 else None
-    ev = self._aot_events('spx_potrf')
-    _check(self.lib.spx_potrf(spx_dtype(dt), n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(L.data_ptr()),
-                              ldl, ctypes.c_void_p(info.data_ptr()), _ptr(ws), ws.numel() if ws is not None else 0,
-                              self.stream()), 'spx_potrf')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_potrf', spx_dtype(dt), n, _ptr(A), lda, _ptr(L), ldl, _ptr(info), _ptr(ws), nws)
     return info
 
   def trsm(self, L, B, side='L', trans=False):
@@ -1449,18 +993,11 @@ class HipBackend:
     nl = m if side == 'L' else n
     _, _, ldl = self._matrix('trsm: L', L, nl, nl, dt)
     sd = 0 if side == 'L' else 1
-    need = self.lib.spx_trsm_workspace(spx_dtype(dt), sd, m, n)
-    if need < 0:
-      raise ValueError('trsm: bad sizes (%d, %d)' % (m, n))
+    ws, nws = self._workspace_for('spx_trsm_workspace', (spx_dtype(dt), sd, m, n), B.device,
+                                  'trsm: bad sizes (%d, %d)' % (m, n))
     if m == 0 or n == 0:
       return
-    ws = self._workspace(int(need), B.device) if need > 0 else None
-    ev = self._aot_events('spx_trsm')
-    _check(self.lib.spx_trsm(spx_dtype(dt), sd, 1 if trans else 0, m, n, ctypes.c_void_p(L.data_ptr()), ldl,
-                             ctypes.c_void_p(B.data_ptr()), ldb, _ptr(ws), ws.numel() if ws is not None else 0,
-                             self.stream()), 'spx_trsm')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_trsm', spx_dtype(dt), sd, 1 if trans else 0, m, n, _ptr(L), ldl, _ptr(B), ldb, _ptr(ws), nws)
 
   def syrk(self, A, B, C, lower=False):
     """``C`` (M, N) -= ``A`` (M, K) @ ``B`` (N, K)^T (spx_syrk).  ``lower``
@@ -1473,12 +1010,7 @@ class HipBackend:
       raise ValueError('syrk: lower needs a square C, got (%d, %d)' % (M, N))
     if M == 0 or N == 0 or K == 0:
       return
-    ev = self._aot_events('spx_syrk')
-    _check(self.lib.spx_syrk(spx_dtype(dt), 1 if lower else 0, M, N, K, ctypes.c_void_p(A.data_ptr()), lda,
-                             ctypes.c_void_p(B.data_ptr()), ldb, ctypes.c_void_p(C.data_ptr()), ldc, self.stream()),
-           'spx_syrk')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_syrk', spx_dtype(dt), 1 if lower else 0, M, N, K, _ptr(A), lda, _ptr(B), ldb, _ptr(C), ldc)
 
   # ------------------------------------------------------------------- qr
   def geqr(self, A):
@@ -1502,11 +1034,7 @@ class HipBackend:
     handle = QrHandle(ws, m, n, dt)
     if m == 0 or n == 0:
       return R, handle
-    ev = self._aot_events('spx_geqr')
-    _check(self.lib.spx_geqr(spx_dtype(dt), m, n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(R.data_ptr()),
-                             n, _ptr(ws), ws.numel(), self.stream()), 'spx_geqr')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_geqr', spx_dtype(dt), m, n, _ptr(A), lda, _ptr(R), n, _ptr(ws), ws.numel())
     return R, handle
 
   def orgqr(self, handle, C, Q):
@@ -1522,11 +1050,8 @@ class HipBackend:
       _, _, ldc = self._matrix('orgqr: C', C, n, n, dt)
     if m == 0 or n == 0:
       return
-    ev = self._aot_events('spx_orgqr')
-    _check(self.lib.spx_orgqr(spx_dtype(dt), m, n, _ptr(handle.workspace), handle.workspace.numel(), _ptr(C), ldc,
-                              ctypes.c_void_p(Q.data_ptr()), ldq, self.stream()), 'spx_orgqr')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_orgqr', spx_dtype(dt), m, n, _ptr(handle.workspace), handle.workspace.numel(), _ptr(C), ldc,
+               _ptr(Q), ldq)
 
   # ------------------------------------------------------------------ eigh
   def syevj(self, A, uplo='L'):
@@ -1562,12 +1087,8 @@ class HipBackend:
     info = torch.zeros((batch,), dtype=torch.int32, device=A.device)
     if batch == 0 or n == 0:
       return W, V, info
-    ev = self._aot_events('spx_syevj')
-    _check(self.lib.spx_syevj(spx_dtype(dt), 0 if uplo == 'L' else 1, batch, n, ctypes.c_void_p(A.data_ptr()), lda,
-                              stride_a, ctypes.c_void_p(W.data_ptr()), n, ctypes.c_void_p(V.data_ptr()), n, n * n,
-                              ctypes.c_void_p(info.data_ptr()), self.stream()), 'spx_syevj')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_syevj', spx_dtype(dt), 0 if uplo == 'L' else 1, batch, n, _ptr(A), lda, stride_a, _ptr(W), n,
+               _ptr(V), n, n * n, _ptr(info))
     return W, V, info
 
   # --------------------------------------------------------------- sparse
@@ -1611,13 +1132,9 @@ class HipBackend:
     ws = workspace if workspace is not None else CsrWorkspace()
     if ws.buf is None or ws.buf.numel() < need or ws.buf.device != val.device:
       ws.buf, ws.prepared = torch.empty((need,), dtype=torch.uint8, device=val.device), False
-    ev = self._aot_events('spx_csrmm')
-    _check(self.lib.spx_csrmm(spx_dtype(dt), m, int(n), p, nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(B), ldb,
-                              _ptr(C), ldc, float(alpha), float(beta), int(g), _ptr(ws.buf), ws.buf.numel(),
-                              1 if ws.prepared else 0, self.stream()), 'spx_csrmm')
+    self._call('spx_csrmm', spx_dtype(dt), m, int(n), p, nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(B), ldb,
+               _ptr(C), ldc, float(alpha), float(beta), int(g), _ptr(ws.buf), ws.buf.numel(), 1 if ws.prepared else 0)
     ws.prepared = True
-    if ev is not None:
-      ev[1].record()
 
   def csr_todense(self, rowptr, col, val, n, D):
     """``D`` (m, n), possibly padded, = the CSR matrix as a dense block
@@ -1626,11 +1143,7 @@ class HipBackend:
     _, _, ldd = self._matrix('csr_todense: D', D, m, int(n), dt)
     if m == 0 or n == 0:
       return
-    ev = self._aot_events('spx_csr_todense')
-    _check(self.lib.spx_csr_todense(spx_dtype(dt), m, int(n), nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(D), ldd,
-                                    self.stream()), 'spx_csr_todense')
-    if ev is not None:
-      ev[1].record()
+    self._call('spx_csr_todense', spx_dtype(dt), m, int(n), nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(D), ldd)
 
   @staticmethod
   def _kmeans_counters_offset(D):
@@ -1682,8 +1195,11 @@ def _cls(stride):
   return 'c' if stride == 1 else ('b' if stride == 0 else 'g')
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+def _dense(what, t, dtype, numel, size):
+  """ValueError unless ``t`` is a contiguous ``dtype`` tensor of ``numel``
+  elements (``size``: how the message words that count)."""
+  if np_dtype(t.dtype) != dtype or not t.is_contiguous() or t.numel() != numel:
+    raise ValueError('%s must be a contiguous %s tensor of %s' % (what, dtype, size))
 
 
 def _vec_aligned(t, strides, cls, V):

@@ -28,6 +28,8 @@ import os
 import zlib
 
 from . import runtime
+# the shared ABI helpers, under the short names the collectives below use
+from .binding import _check, _ptr as _p, current_stream as _stream, load_library as _lib, np_dtype, spx_dtype
 
 _OPS = {'sum': 'SUM', 'min': 'MIN', 'max': 'MAX'}
 _SPX_OP = {'sum': 0, 'min': 1, 'max': 2}
@@ -60,28 +62,8 @@ def _staged(ctx, t):
 
 
 # ------------------------------------------------------- libspx RCCL plane
-def _lib():
-  from . import backend
-  return backend.load_library()
-
-
-def _check(rc, what):
-  if rc != 0:
-    raise RuntimeError('%s failed (%d): %s' % (what, rc, _lib().spx_last_error().decode()))
-
-
 def _dt(t):
-  from . import backend
-  return backend.spx_dtype(backend.np_dtype(t.dtype))
-
-
-def _stream():
-  import torch
-  return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _p(t):
-  return ctypes.c_void_p(t.data_ptr())
+  return spx_dtype(np_dtype(t.dtype))
 
 
 def rccl_path():

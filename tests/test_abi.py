@@ -41,6 +41,78 @@ def test_python_binding_signatures_cover_header():
   assert sorted(backend.EXPORTED) == declared()
 
 
+C_CLASS = {'int': 'i4', 'int32_t': 'i4', 'uint32_t': 'i4', 'int64_t': 'i8', 'uint64_t': 'i8', 'size_t': 'i8',
+           'double': 'f8'}
+
+
+def prototypes():
+  """{name: (return class, [argument classes])} of every prototype in
+  include/spx.h: 'p' for a pointer, else the kind and the bytes of the type."""
+  src = open(os.path.join(ROOT, 'include', 'spx.h')).read()
+  src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
+  src = re.sub(r'//[^\n]*', ' ', src)
+  src = '\n'.join(line for line in src.split('\n') if not line.lstrip().startswith('#'))
+
+  def cls(decl, named):
+    if '*' in decl or '[' in decl:
+      return 'p'
+    words = [w for w in decl.split() if w not in ('const', 'unsigned', 'signed')]
+    assert len(words) == (2 if named else 1), decl
+    return C_CLASS[words[0]]
+
+  out = {}
+  for ret, name, args in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(spx_\w+)\s*\(([^()]*)\)\s*;', src):
+    args = [a.strip() for a in args.split(',')] if args.strip() not in ('', 'void') else []
+    assert name not in out, name
+    out[name] = (cls(ret, False), [cls(a, True) for a in args])
+  return out
+
+
+def ctypes_class(t):
+  if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+    return 'p'
+  return ('f' if t in (ctypes.c_float, ctypes.c_double) else 'i') + str(ctypes.sizeof(t))
+
+
+def test_python_binding_signatures_match_header_prototypes():
+  """Every prototype of include/spx.h has an entry in the binding's ctypes
+  table with the same arity and, per argument and for the result, the same
+  class: pointer, or integer / float of the same width.  A wrong width or a
+  missing argument there would corrupt a call silently.  (Needs neither the
+  built library nor a GPU.)"""
+  from spartan_amd import binding
+  protos = prototypes()
+  assert sorted(protos) == declared() and len(protos) >= 67
+  for name, (ret, args) in protos.items():
+    assert name in binding._SIGS, name
+    argtypes, restype = binding._SIGS[name]
+    assert len(argtypes) == len(args), (name, len(argtypes), len(args))
+    assert [ctypes_class(t) for t in argtypes] == args, name
+    assert ctypes_class(restype) == ret, name
+  # and the parser tells the classes apart
+  assert protos['spx_last_error'] == ('p', []) and protos['spx_kmeans_assign_workspace'] == ('i8', ['i4'] + ['i8'] * 3)
+  assert protos['spx_gemm'][1][-3:] == ['f8', 'f8', 'p'] and protos['spx_launch'][1][1] == 'i4'
+
+
+def test_binding_module_stands_alone():
+  """spartan_amd/binding.py imports nothing else of the package: loaded by its
+  path in a fresh interpreter it brings in neither the backend nor codegen,
+  and the table and the dtype codes are there without a GPU."""
+  import subprocess
+  import sys
+  code = r'''
+import importlib.util, sys
+spec = importlib.util.spec_from_file_location('binding', %r)
+m = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(m)
+assert len(m.EXPORTED) >= 67 and m.spx_dtype('float32') == m.SPX_F32
+assert not [k for k in sys.modules if k.startswith('spartan_amd') or k == 'torch'], sorted(sys.modules)
+print('ok')
+''' % os.path.join(ROOT, 'spartan_amd', 'binding.py')
+  r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
+  assert r.returncode == 0 and r.stdout.strip().endswith('ok'), r.stderr[-2000:]
+
+
 @pytest.mark.skipif(not os.path.exists(LIB), reason='libspx.so not built')
 def test_argument_validation_without_gpu():
   """Invalid arguments are rejected before any device work (error codes + message)."""

@@ -1914,3 +1914,52 @@ def test_kmeans_step_timing_hook(ex):
   assert torch.equal(sums, s0) and torch.equal(lab, l0)
   with pytest.raises(RuntimeError):
     be.kmeans_times()                # timing is off
+
+
+def test_kernel_events_log_the_timed_aot_calls(ex):
+  """The timing contract bench.py reads (``kernel_events``): each timed
+  ahead-of-time call logs one (name, start, end) triple in call order, the
+  untimed ones (fill, copy_region, bincount) and an early return on an empty
+  input log nothing, and with the list off nothing is logged or raised."""
+  import math
+  import torch
+  from spartan_amd import backend
+  be = backend.get()
+
+  def dev(shape, dtype, fill=1):
+    return torch.full(shape, fill, dtype=dtype, device='cuda')
+
+  A, B, C = dev((4, 4), torch.float32), dev((4, 4), torch.float32), dev((4, 4), torch.float32)
+  src_i, out_i = dev((8,), torch.int32), dev((8,), torch.int64)
+  src_f, out_f = torch.arange(8, 0, -1, dtype=torch.float32, device='cuda'), dev((8,), torch.float32)
+  A64, B64, C64 = dev((4, 4), torch.float64), dev((4, 4), torch.float64), dev((4, 4), torch.float64)
+  filled = dev((8,), torch.float32, 0)
+  dst, blk = dev((2, 2), torch.float32, 0), dev((2, 2), torch.float32)
+  labels, counts = dev((8,), torch.int64), dev((2,), torch.int64, 0)
+  empty = torch.empty((0,), dtype=torch.float32, device='cuda')
+  be.kernel_events = []
+  try:
+    be.gemm(A, B, C)
+    be.fill(filled, backend.FILL_CONST, 3.0, 0.0, 0, (0,), (8,))
+    be.scan(src_i, out_i, (1, 8, 1))
+    be.copy_region(dst, (0, 0), blk, (0, 0), (2, 2))
+    be.sort(src_f, out_f, None, (1, 8, 1))
+    be.sort(empty, torch.empty_like(empty), None, (0, 8, 1))
+    be.bincount(labels, counts)
+    be.syrk(A64, B64, C64)
+    events = be.kernel_events
+  finally:
+    be.kernel_events = None
+  torch.cuda.synchronize()
+  assert [e[0] for e in events] == ['spx_gemm', 'spx_scan', 'spx_sort', 'spx_syrk']
+  for e in events:
+    assert len(e) == 3
+    ms = e[1].elapsed_time(e[2])
+    assert isinstance(ms, float) and math.isfinite(ms) and ms >= 0.0, e
+  # the calls themselves ran: what each one wrote
+  assert torch.equal(C, dev((4, 4), torch.float32, 4)) and torch.equal(filled, dev((8,), torch.float32, 3))
+  assert out_i.tolist() == list(range(1, 9)) and out_f.tolist() == [float(v) for v in range(1, 9)]
+  assert torch.equal(dst, blk) and counts.tolist() == [0, 8]
+  assert torch.equal(C64, dev((4, 4), torch.float64, -3))
+  be.gemm(A, B, C)
+  assert be.kernel_events is None
