@@ -35,7 +35,7 @@ extern "C" {
  * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
- * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj */
+ * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan */
 
 /* error codes */
 #define SPX_OK 0
@@ -149,6 +149,32 @@ int spx_copy_region(int dst_dtype, void* dst, const int64_t* dst_shape,
 int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
              const void* B, int64_t ldb, void* C, int64_t ldc, double alpha,
              double beta, void* stream);
+
+/* spx_gemm_plan (pure host): the route spx_gemm takes for these arguments --
+ * both call the one selection function.  A and B are looked at for their
+ * address bits only (16-byte alignment) and never dereferenced, so any
+ * non-null value will do.  Any output may be NULL.
+ *   kernel   SPX_GEMM_*: which kernel runs (NONE: M == 0 or N == 0, no launch)
+ *   aligned  1: the instantiation without bounds checks (whole block tiles,
+ *            16-byte aligned operands and rows); 0: the bounds-checked one
+ *   bm, bn, bk  the block tile and the K-tile
+ *   flush_k  the K distance after which the kernel's accumulators go into C
+ *            (fp32: 512 K-tiles; F64_P3: one launch per 8192 of K); 0 for the
+ *            kernels whose one chain spans any K
+ * Returns the argument errors of spx_gemm (those about C and ldc aside).
+ * The choice between the two- and the three-stage kernels follows
+ * SPX_GEMM_P3 in the environment (read once per process): 0 never, 1 (the
+ * default) fp32 only, 2 fp64 too. */
+#define SPX_GEMM_NONE 0
+#define SPX_GEMM_INT 1        /* k_gemm_int, 16x16 tiles                       */
+#define SPX_GEMM_F32_SMALL 2  /* two-stage 128x128x16, < 512 256x256 tiles     */
+#define SPX_GEMM_F32_BIG 3    /* two-stage 256x128x16                          */
+#define SPX_GEMM_F32_P3 4     /* three-stage 256x256x16, aligned products only */
+#define SPX_GEMM_F64 5        /* two-stage 128x128x16                          */
+#define SPX_GEMM_F64_P3 6     /* three-stage 128x128x16 (experimental)         */
+int spx_gemm_plan(int dtype, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
+                  const void* B, int64_t ldb, int64_t* kernel, int64_t* aligned,
+                  int64_t* bm, int64_t* bn, int64_t* bk, int64_t* flush_k);
 
 /* ------------------------------------------------- arg-reduction combine
  * Element-wise combine of R (value, index) partial sets, e.g. gathered from

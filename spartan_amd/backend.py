@@ -28,8 +28,8 @@ from .layout import broadcast_strides, coalesce, reduce_view, contiguous_strides
 from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP_CODE, FILL_CONST, FILL_ARANGE,
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
-                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, current_stream,
-                     _arr, _check, _k_limit, _ptr)
+                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, gemm_plan,
+                     GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -81,6 +81,7 @@ def _signatures():
       'spx_merge': ([I, I, VP, VP, I, _I64P, _I64P, _I64P, VP, I, I, VP], I),
       'spx_copy_region': ([I, VP, _I64P, _I64P, I, VP, _I64P, _I64P, I, _I64P, VP], I),
       'spx_gemm': ([I, I64, I64, I64, VP, I64, VP, I64, VP, I64, F64, F64, VP], I),
+      'spx_gemm_plan': ([I, I64, I64, I64, VP, I64, VP, I64] + [_I64P] * 6, I),
       'spx_argreduce_combine': ([I, I, VP, VP, I64, I64, VP, VP, VP], I),
       'spx_kmeans_assign_workspace': ([I, I64, I64, I64], I64),
       'spx_kmeans_assign': ([I, I64, I64, I64, VP, I64, VP, VP, VP, VP, SZ, I, VP], I),
@@ -301,6 +302,27 @@ def compact_tile():
     else:
       hi = mid
   return lo
+
+
+GEMM_KERNELS = ('NONE', 'INT', 'F32_SMALL', 'F32_BIG', 'F32_P3', 'F64', 'F64_P3')  # SPX_GEMM_* of include/spx.h
+
+
+def gemm_plan(dtype, M, N, K, a_ptr=256, lda=None, b_ptr=256, ldb=None):
+  """The route spx_gemm takes for an (M, K) @ (K, N) product of ``dtype``
+  (spx_gemm_plan, the library's own selection): a dict of 'kernel' (a name of
+  GEMM_KERNELS), 'aligned' (the instantiation without bounds checks), the
+  block tile 'bm', 'bn', 'bk' and 'flush_k' (the K distance between the
+  kernel's flushes into C; 0: one chain over any K).  ``a_ptr`` / ``b_ptr``
+  are addresses (``tensor.data_ptr()``) of which only the alignment counts,
+  ``lda`` / ``ldb`` the row strides in elements (default: contiguous)."""
+  lda, ldb = (K if lda is None else lda), (N if ldb is None else ldb)
+  v = [ctypes.c_int64(0) for _ in range(6)]
+  rc = load_library().spx_gemm_plan(spx_dtype(dtype), int(M), int(N), int(K), ctypes.c_void_p(int(a_ptr)), int(lda),
+                                    ctypes.c_void_p(int(b_ptr)), int(ldb), *[ctypes.byref(x) for x in v])
+  if rc != 0:
+    raise ValueError('gemm_plan (%d): %s' % (rc, _lib.spx_last_error().decode()))
+  kernel, aligned, bm, bn, bk, flush_k = (int(x.value) for x in v)
+  return {'kernel': GEMM_KERNELS[kernel], 'aligned': bool(aligned), 'bm': bm, 'bn': bn, 'bk': bk, 'flush_k': flush_k}
 
 
 def _float_plan(op, kernel, dtype, nout, sizes=(), negative=None):

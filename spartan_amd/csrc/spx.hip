@@ -697,19 +697,80 @@ __global__ __launch_bounds__(256) void k_gemm_int(i64 M, i64 N, i64 K, const T* 
   }
 }
 
+// The route of a product: which kernel, which instantiation, its block tile
+// and the K distance between its flushes into C.  Pure host code -- A and B
+// are looked at for their address bits only -- shared by spx_gemm and
+// spx_gemm_plan, so what the plan answers is what the call launches.
+struct GemmRoute {
+  int kernel = SPX_GEMM_NONE;
+  bool aligned = false;
+  int bm = 0, bn = 0, bk = 0;
+  i64 flush_k = 0;
+};
+// the argument checks of spx_gemm in its order (C and ldc only for the call
+// itself: with_c), then the selection; route.kernel stays SPX_GEMM_NONE where
+// there is nothing to launch (M == 0 or N == 0)
+static int gemm_route(const char* who, int dtype, i64 M, i64 N, i64 K, const void* A, i64 lda, const void* B, i64 ldb,
+                      bool with_c, const void* C, i64 ldc, GemmRoute& r) {
+  if (dtype != SPX_F32 && dtype != SPX_F64 && dtype != SPX_I32 && dtype != SPX_I64)
+    return set_err(SPX_ENOTSUP, "%s: dtype %d not supported (F32/F64/I32/I64)", who, dtype);
+  if (M < 0 || N < 0 || K < 0) return set_err(SPX_EINVAL, "%s: negative dimension", who);
+  if (lda < K || ldb < N || (with_c && ldc < N)) return set_err(SPX_EINVAL, "%s: leading dimension too small", who);
+  if (M == 0 || N == 0) return SPX_OK;
+  if (!A || !B || (with_c && !C)) return set_err(SPX_EINVAL, "%s: null pointer", who);
+  if (K == 0) {  // C = beta * C
+    return set_err(SPX_ENOTSUP, "%s: K == 0 not supported", who);
+  }
+  auto set = [&](int kernel, bool aligned, int bm, int bn, int bk, i64 flush_k) {
+    r.kernel = kernel, r.aligned = aligned, r.bm = bm, r.bn = bn, r.bk = bk, r.flush_k = flush_k;
+  };
+  if (dtype == SPX_I32 || dtype == SPX_I64) {
+    set(SPX_GEMM_INT, false, 16, 16, 16, 0);
+  } else if (dtype == SPX_F32) {
+    i64 big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
+    if (big_tiles >= 512 && big_tiles <= 0x7fffffffLL && gemm_p3_on() && spx_mfma::p3_ok(M, N, K, A, lda, B, ldb)) {
+      set(SPX_GEMM_F32_P3, true, 256, 256, 16, (i64)SPX_GEMM_GFL * 16);
+    } else if (big_tiles >= 512) {
+      if (big_tiles > 0x7fffffffLL) return set_err(SPX_EINVAL, "%s: too many tiles", who);
+      set(SPX_GEMM_F32_BIG, GemmF32Big::is_aligned(M, N, K, A, lda, B, ldb), GemmF32Big::bm, GemmF32Big::bn,
+          GemmF32Big::bk, (i64)SPX_GEMM_GFL * GemmF32Big::bk);
+    } else {
+      set(SPX_GEMM_F32_SMALL, GemmF32Small::is_aligned(M, N, K, A, lda, B, ldb), GemmF32Small::bm, GemmF32Small::bn,
+          GemmF32Small::bk, (i64)SPX_GEMM_GFL * GemmF32Small::bk);
+    }
+  } else {
+    i64 tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    if (tiles > 0x7fffffffLL) return set_err(SPX_EINVAL, "%s: too many tiles", who);
+    if (tiles >= 1024 && gemm_p3_on() > 1 && spx_mfma::p3d_ok<16>(M, N, K, A, lda, B, ldb))
+      set(SPX_GEMM_F64_P3, true, 128, 128, 16, SPX_GEMM_KCHUNK);
+    else
+      set(SPX_GEMM_F64, GemmF64::is_aligned(M, N, K, A, lda, B, ldb), GemmF64::bm, GemmF64::bn, GemmF64::bk, 0);
+  }
+  return SPX_OK;
+}
+
+extern "C" int spx_gemm_plan(int dtype, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                             int64_t ldb, int64_t* kernel, int64_t* aligned, int64_t* bm, int64_t* bn, int64_t* bk,
+                             int64_t* flush_k) {
+  GemmRoute r;
+  const int rc = gemm_route("spx_gemm_plan", dtype, M, N, K, A, lda, B, ldb, false, nullptr, 0, r);
+  if (rc != SPX_OK) return rc;
+  if (kernel) *kernel = r.kernel;
+  if (aligned) *aligned = r.aligned ? 1 : 0;
+  if (bm) *bm = r.bm;
+  if (bn) *bn = r.bn;
+  if (bk) *bk = r.bk;
+  if (flush_k) *flush_k = r.flush_k;
+  return SPX_OK;
+}
+
 extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
                         const void* B, int64_t ldb, void* C, int64_t ldc, double alpha,
                         double beta, void* stream) {
-  if (dtype != SPX_F32 && dtype != SPX_F64 && dtype != SPX_I32 && dtype != SPX_I64)
-    return set_err(SPX_ENOTSUP, "spx_gemm: dtype %d not supported (F32/F64/I32/I64)", dtype);
-  if (M < 0 || N < 0 || K < 0) return set_err(SPX_EINVAL, "spx_gemm: negative dimension");
-  if (lda < K || ldb < N || ldc < N) return set_err(SPX_EINVAL, "spx_gemm: leading dimension too small");
-  if (M == 0 || N == 0) return SPX_OK;
-  if (!A || !B || !C) return set_err(SPX_EINVAL, "spx_gemm: null pointer");
-  if (K == 0) {  // C = beta * C
-    return set_err(SPX_ENOTSUP, "spx_gemm: K == 0 not supported");
-  }
-  if (dtype == SPX_I32 || dtype == SPX_I64) {
+  GemmRoute r;
+  const int rc = gemm_route("spx_gemm", dtype, M, N, K, A, lda, B, ldb, true, C, ldc, r);
+  if (rc != SPX_OK || r.kernel == SPX_GEMM_NONE) return rc;
+  if (r.kernel == SPX_GEMM_INT) {
     dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 15) / 16));
     if (dtype == SPX_I64)
       k_gemm_int<int64_t><<<grid, 256, 0, S(stream)>>>(M, N, K, (const int64_t*)A, lda, (const int64_t*)B, ldb,
@@ -729,32 +790,28 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
       LAUNCH_CHECK("spx_gemm(scale C)");
       beta = 1.0;
     }
-    i64 big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
-    if (big_tiles >= 512 && big_tiles <= 0x7fffffffLL && gemm_p3_on() && spx_mfma::p3_ok(M, N, K, A, lda, B, ldb)) {
+    if (r.kernel == SPX_GEMM_F32_P3) {
       // one launch, K in chunks of SPX_GEMM_GFL K-tiles inside the kernel
       // (beta is 0 or 1 here, as the flush needs)
       e = spx_mfma::p3_launch<8, 0, SPX_GEMM_GFL, 1, 4>(M, N, K, a, lda, b, ldb, (float*)C, ldc, (float)alpha,
                                                          (float)beta, S(stream));
-    } else if (big_tiles >= 512) {
-      if (big_tiles > 0x7fffffffLL) return set_err(SPX_EINVAL, "spx_gemm: too many tiles");
-      e = GemmF32Big::launch(M, N, K, a, lda, b, ldb, (float*)C, ldc, (float)alpha, (float)beta,
-                             GemmF32Big::is_aligned(M, N, K, A, lda, B, ldb), S(stream));
+    } else if (r.kernel == SPX_GEMM_F32_BIG) {
+      e = GemmF32Big::launch(M, N, K, a, lda, b, ldb, (float*)C, ldc, (float)alpha, (float)beta, r.aligned,
+                             S(stream));
     } else {
-      e = GemmF32Small::launch(M, N, K, a, lda, b, ldb, (float*)C, ldc, (float)alpha, (float)beta,
-                               GemmF32Small::is_aligned(M, N, K, A, lda, B, ldb), S(stream));
+      e = GemmF32Small::launch(M, N, K, a, lda, b, ldb, (float*)C, ldc, (float)alpha, (float)beta, r.aligned,
+                               S(stream));
     }
     if (e != hipSuccess) return set_err(SPX_EHIP, "spx_gemm(f32) launch failed: %s", hipGetErrorString(e));
   } else {
-    i64 tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    if (tiles > 0x7fffffffLL) return set_err(SPX_EINVAL, "spx_gemm: too many tiles");
-    if (tiles >= 1024 && gemm_p3_on() > 1 && spx_mfma::p3d_ok<16>(M, N, K, A, lda, B, ldb)) {
-      const double *a = (const double*)A, *b = (const double*)B;
+    const double *a = (const double*)A, *b = (const double*)B;
+    if (r.kernel == SPX_GEMM_F64_P3) {
       e = gemm_kchunks<double>(K, a, b, ldb, beta, [&](i64 kc, const double* ak, const double* bk, double bt) {
         return spx_mfma::p3d_launch<8, 16, 0, 4>(M, N, kc, ak, lda, bk, ldb, (double*)C, ldc, alpha, bt, S(stream));
       });
-    } else
-    e = GemmF64::launch(M, N, K, (const double*)A, lda, (const double*)B, ldb, (double*)C, ldc, alpha, beta,
-                        GemmF64::is_aligned(M, N, K, A, lda, B, ldb), S(stream));
+    } else {
+      e = GemmF64::launch(M, N, K, a, lda, b, ldb, (double*)C, ldc, alpha, beta, r.aligned, S(stream));
+    }
     if (e != hipSuccess) return set_err(SPX_EHIP, "spx_gemm(f64) launch failed: %s", hipGetErrorString(e));
   }
   return SPX_OK;
