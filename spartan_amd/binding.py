@@ -40,7 +40,9 @@ _TORCH_DT, _NP_DT = {}, {}  # NumPy dtype <-> torch dtype, filled on first use (
 
 def _dtype_tables():
   import torch
-  pairs = [(np.dtype(name), getattr(torch, name)) for name in ('bool', 'int32', 'int64', 'float32', 'float64')]
+  # (int8 / uint8 / int16: generated kernels only -- codegen.CTYPE lowers them, spx_dtype does not take them)
+  pairs = [(np.dtype(name), getattr(torch, name))
+           for name in ('bool', 'int32', 'int64', 'float32', 'float64', 'int8', 'uint8', 'int16')]
   _NP_DT.update((t, d) for d, t in pairs)
   _TORCH_DT.update(pairs)
 

@@ -100,7 +100,8 @@ class Op:
     self.name = name
     self.args = list(args)
     uf = getattr(np, name)
-    keys = tuple(a.pytype if isinstance(a, Sc) else a.dtype for a in self.args)
+    # weak Python int / float scalars; a Python bool is NumPy's bool, not weak
+    keys = tuple(a.pytype if isinstance(a, Sc) and a.pytype is not bool else a.dtype for a in self.args)
     try:
       res = uf.resolve_dtypes(keys + (None,) * uf.nout)
     except Exception as e:  # pragma: no cover - numpy raises for invalid combos
@@ -232,6 +233,13 @@ class Emitter:
     self.ocml.add((full, ctype(dt), len(args)))
     return '%s(%s)' % (full, ', '.join(args))
 
+  def divmod_call(self, fname, dt, args):
+    """Float ``//`` / ``%``: fdiv_py / fmod_py, the two results of divmod_py
+    (_ocml_decls emits them for every type whose copysign is declared)."""
+    for f, n in (('fmod', 2), ('floor', 1), ('copysign', 2)):
+      self.ocml_call(f, dt, ['0'] * n)
+    return '%s(%s, %s)' % (fname, args[0], args[1])
+
   def emit(self, node, leaf):
     """Return a C expression (usually a temporary) of node.dtype."""
     if isinstance(node, In):
@@ -265,11 +273,11 @@ class Emitter:
       return '%s / %s' % (a[0], a[1])
     if name == 'floor_divide':
       if fl:
-        return self.ocml_call('floor', T, ['%s / %s' % (a[0], a[1])])
+        return self.divmod_call('fdiv_py', T, a)
       return 'fdiv_i(%s, %s)' % (a[0], a[1])
     if name in ('remainder', 'mod'):
       if fl:
-        return 'fmod_py(%s, %s)' % (a[0], a[1]) if self.ocml_call('fmod', T, [a[0], a[1]]) else ''
+        return self.divmod_call('fmod_py', T, a)
       return 'fmod_i(%s, %s)' % (a[0], a[1])
     if name == 'negative':
       return '-%s' % a[0]
@@ -293,7 +301,14 @@ class Emitter:
             a[0], a[0], a[0], a[1], a[1], a[1], a[0], cmp, a[1], a[0], a[1])
       return '(%s %s %s ? %s : %s)' % (a[0], cmp, a[1], a[0], a[1])
     if name in ('fmax', 'fmin'):
-      return self.ocml_call(name, T, [a[0], a[1]])
+      cmp = '>' if name == 'fmax' else '<'
+      if fl:
+        # a NaN loses to a number; on a tie (+0 against -0) the second operand
+        # wins like in np.fmax / np.fmin and in maximum / minimum above (the
+        # library's fmax orders the zeros: fmax(+0, -0) came out +0, NumPy's -0)
+        return '((%s %s %s || %s != %s) ? %s : %s)' % (a[0], cmp, a[1], a[1], a[1], a[0], a[1])
+      # integers and bools have no NaN: np.fmax / np.fmin are maximum / minimum
+      return '(%s %s %s ? %s : %s)' % (a[0], cmp, a[1], a[0], a[1])
     cmps = {'equal': '==', 'not_equal': '!=', 'less': '<', 'less_equal': '<=', 'greater': '>',
             'greater_equal': '>='}
     if name in cmps:
@@ -306,6 +321,8 @@ class Emitter:
       return '(u8)((%s != 0) != (%s != 0))' % (a[0], a[1])
     if name == 'logical_not':
       return '(u8)(%s == 0)' % a[0]
+    if name in ('isnan', 'isinf', 'isfinite') and not fl:
+      return '(u8)%d' % (name == 'isfinite')  # integers and bools are always finite
     if name == 'isnan':
       return '(u8)(%s != %s)' % (a[0], a[0])
     if name == 'isinf':
@@ -316,6 +333,9 @@ class Emitter:
       if fl:
         return self.ocml_call('pow', T, [a[0], a[1]])
       return 'ipow(%s, %s)' % (a[0], a[1])
+    if name in ('expm1', 'log1p') and fl:
+      # the library's expm1(-0.0) and log1p(-0.0) are +0.0; NumPy (and C) keep the sign
+      return '(%s == 0 ? %s : %s)' % (a[0], a[0], self.ocml_call(OCML_1[name], T, [a[0]]))
     if name in OCML_1 and fl:
       return self.ocml_call(OCML_1[name], T, [a[0]])
     if name in OCML_2 and fl:
@@ -376,15 +396,41 @@ class KArgs(ctypes.Structure):
   ]
 
 
+# NumPy's float divmod (npy_divmod): the quotient is computed from fmod's exact
+# remainder, (a - mod) / b, and snapped to the nearest integer -- floor(a / b)
+# differs wherever a / b rounds up to an integer (1.0 // 0.1 is 9, floor(1.0 /
+# 0.1) is 10); a zero remainder takes the divisor's sign, a zero quotient the
+# sign of a / b; b == 0 gives a / b and fmod's NaN.
+DIVMOD_PY = '''DEV %(T)s divmod_py(%(T)s a, %(T)s b, %(T)s& mod_out) {
+  %(T)s mod = __ocml_fmod%(S)s(a, b);
+  if (b == 0) { mod_out = mod; return a / b; }
+  %(T)s div = (a - mod) / b;
+  if (mod != 0) {
+    if ((b < 0) != (mod < 0)) { mod = mod + b; div = div - (%(T)s)1; }
+  } else {
+    mod = __ocml_copysign%(S)s((%(T)s)0, b);
+  }
+  %(T)s fd;
+  if (div != 0) {
+    fd = __ocml_floor%(S)s(div);
+    if (div - fd > (%(T)s)0.5) fd = fd + (%(T)s)1;
+  } else {
+    fd = __ocml_copysign%(S)s((%(T)s)0, a / b);
+  }
+  mod_out = mod;
+  return fd;
+}
+DEV %(T)s fdiv_py(%(T)s a, %(T)s b) { %(T)s m; return divmod_py(a, b, m); }
+DEV %(T)s fmod_py(%(T)s a, %(T)s b) { %(T)s m; divmod_py(a, b, m); return m; }'''
+
+
 def _ocml_decls(ocml):
   out = []
   for full, ct, nargs in sorted(ocml):
     out.append('extern "C" __attribute__((device)) %s %s(%s);' % (ct, full, ', '.join([ct] * nargs)))
-  if any(f.startswith('__ocml_fmod') for f, _, _ in ocml):
-    for full, ct, nargs in sorted(ocml):
-      if full.startswith('__ocml_fmod'):
-        out.append('DEV %s fmod_py(%s a, %s b) { %s r = %s(a, b); if (r != 0 && ((r < 0) != (b < 0))) r += b; return r; }'
-                   % (ct, ct, ct, ct, full))
+  for full, ct, nargs in sorted(ocml):
+    if full.startswith('__ocml_copysign'):
+      out.append(DIVMOD_PY % {'T': ct, 'S': full[len('__ocml_copysign'):]})
   return '\n'.join(out)
 
 

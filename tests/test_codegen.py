@@ -154,6 +154,61 @@ def test_rowdot_interleaved_rows_compile():
                                                    lpr=16, full=True)
 
 
+@pytest.mark.parametrize('dt', [F32, F64])
+def test_float_divmod_prelude_compiles_in_every_skeleton(dt):
+  """Float // and % go through divmod_py (NumPy's npy_divmod over fmod, floor
+  and copysign), declared once per type, in the map and the three reduce
+  skeletons; a plain fmod does not pull it in."""
+  root = Op('add', [Op('floor_divide', [In(0, dt), In(1, dt)]), Op('remainder', [In(0, dt), Sc(0, 0.1)])])
+  ins = [(0, dt), (1, dt)]
+  V = codegen.vec_width([dt])
+  suf = 'f32' if dt == F32 else 'f64'
+  srcs = [codegen.gen_map(root, ins, ['c', 'c'], 1, V, True), codegen.gen_map(root, ins, ['c', 'g'], 2, V, False)]
+  srcs += [codegen.gen_reduce(root, ins, ['c', 'b'], kind, op, V)
+           for kind in ('rows', 'rowsp', 'cols') for op in ('sum', 'max')]
+  for src in srcs:
+    assert src.count('divmod_py(%s a' % codegen.ctype(dt)) == 1
+    assert 'fdiv_py(x0, x1)' in src and 'fmod_py(x0, ' in src
+    for f in ('fmod', 'floor', 'copysign'):
+      assert src.count('__ocml_%s_%s(%s' % (f, suf, codegen.ctype(dt))) == 1  # one declaration
+    _compile(src)
+  plain = codegen.gen_map(Op('fmod', [In(0, dt), In(1, dt)]), ins, ['c', 'c'], 1, V, True)
+  assert 'divmod_py' not in plain
+  # both float types in one kernel: one divmod_py overload each
+  mixed = Op('add', [Op('mod', [In(0, F32), In(1, F32)]), Op('floor_divide', [In(2, F64), In(3, F64)])])
+  src = codegen.gen_map(mixed, [(0, F32), (1, F32), (2, F64), (3, F64)], ['c'] * 4, 1, 2, True)
+  assert src.count('DEV float divmod_py(') == 1 and src.count('DEV double divmod_py(') == 1
+  _compile(src)
+
+
+@pytest.mark.parametrize('dt', [F32, F64, I32, I64, B, np.dtype(np.int8), np.dtype(np.uint8)])
+def test_fmax_fmin_and_float_tests_lower_by_type(dt):
+  """fmax / fmin are compare-selects for every type (floats: with a NaN test
+  of the second operand; never a math-library call with integer arguments);
+  isnan / isinf / isfinite of integers and bools are the constants 0, 0, 1."""
+  ins = [(0, dt), (1, dt)]
+  tests = Op('add', [Op('add', [Cast(Op('isinf', [In(0, dt)]), I32), Cast(Op('isnan', [In(0, dt)]), I32)]),
+                     Cast(Op('isfinite', [In(1, dt)]), I32)])
+  root = Op('add', [Cast(Op('fmin', [Op('fmax', [In(0, dt), In(1, dt)]), In(1, dt)]), F64), Cast(tests, F64)])
+  src = codegen.gen_map(root, ins, ['c', 'c'], 1, codegen.vec_width([dt, F64]), True)
+  assert '__ocml_' not in src
+  if dt.kind == 'f':
+    assert '__builtin_inf()' in src and ' || x1 != x1) ? ' in src
+  else:
+    assert '__builtin_inf' not in src and '!= x1' not in src
+    assert '= (u8)0;' in src and '= (u8)1;' in src
+  _compile(src)
+  _compile(codegen.gen_reduce(root, ins, ['c', 'g'], 'rows', 'max', codegen.vec_width([dt, F64])))
+
+
+def test_bool_scalar_resolves_as_numpy_bool():
+  """A Python bool Sc is NumPy's (strong) bool, not a weak scalar."""
+  assert Op('logical_and', [In(0, B), Sc(0, True)]).dtype == B
+  assert Op('add', [In(0, I32), Sc(0, True)]).dtype == I32
+  assert Op('add', [In(0, B), Sc(0, True)]).dtype == B
+  assert Op('true_divide', [In(0, B), Sc(0, False)]).dtype == F64
+
+
 @pytest.mark.parametrize('unroll', [1, 2, 4])
 def test_dense_map_unroll_compiles(unroll):
   """backend.MAP_UNROLL: U vectors per lane (all loads first) for the dense
