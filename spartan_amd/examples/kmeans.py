@@ -36,7 +36,7 @@ import weakref
 import numpy as np
 
 from .. import backend, comm, expr, runtime
-from ..array import distarray, extent as ext, transfer
+from ..array import blocks, distarray, extent as ext, transfer
 from ..expr.join import register_argmin_fusion, register_join
 
 
@@ -127,7 +127,6 @@ def _deliver_full(target, full):
 
 def _dist_join(kind, arrays, axes, fn_kw, target):
   import torch
-  from ..expr.join import _scatter_updates
   if kind != 'outer' or tuple(axes) != (0, 0) or len(arrays[0].shape) != 2:
     raise NotImplementedError('kmeans_dist_mapper: outer((X, C), (0, 0)) over a 2-d X only')
   X, C = arrays
@@ -135,13 +134,13 @@ def _dist_join(kind, arrays, axes, fn_kw, target):
   be = backend.get()
   c = _replicated_f64(C)
   K, D = c.shape
-  blocks, rows = _local_rows(X, D)
+  row_blocks, rows = _local_rows(X, D)
   dist = {}
   for qi, region, pts in rows:
     dist[qi] = torch.empty((region.shape[0], K), dtype=backend.torch_dtype(target.dtype), device=ctx.device)
     be.cdist(pts, c, dist[qi])
-  _scatter_updates(target, [(qi, ext.create((r.ul[0], 0), (r.lr[0], K), target.shape), src, dist.get(qi))
-                            for qi, (src, r) in enumerate(blocks)])
+  blocks.scatter_updates(target, [(qi, ext.create((r.ul[0], 0), (r.lr[0], K), target.shape), src, dist.get(qi))
+                                  for qi, (src, r) in enumerate(row_blocks)])
 
 
 def _count_join(kind, arrays, axes, fn_kw, target):
@@ -208,13 +207,12 @@ def _assign_fused(arrays, fn_kw, target, dist_dtype):
   counts (of the same single pass over X) the centre / count joins of THAT
   labels array over THAT X take (_PIPE.hand_off) instead of reading X again."""
   import torch
-  from ..expr.join import _scatter_updates
   X, C = arrays
   ctx = runtime.get()
   be = backend.get()
   c = _replicated_f64(C)
   K, D = c.shape
-  blocks, rows = _local_rows(X, D)
+  row_blocks, rows = _local_rows(X, D)
   fused = _step_domain(X, K)
   spec = _PIPE.take_queued(X, K, c, dist_dtype) if fused else None
   if spec is not None:  # the step queued for these very centres (_speculate)
@@ -226,8 +224,8 @@ def _assign_fused(arrays, fn_kw, target, dist_dtype):
     for qi, region, pts in rows:
       labs[qi] = torch.empty((region.shape[0],), dtype=torch.int64, device=ctx.device)
       be.kmeans_assign(pts, c, labs[qi], dist_dtype=dist_dtype)
-  _scatter_updates(target, [(qi, ext.create((r.ul[0],), (r.lr[0],), target.shape), src, labs.get(qi))
-                            for qi, (src, r) in enumerate(blocks)])
+  blocks.scatter_updates(target, [(qi, ext.create((r.ul[0],), (r.lr[0],), target.shape), src, labs.get(qi))
+                                  for qi, (src, r) in enumerate(row_blocks)])
   if fused:
     _PIPE.hand_off(X, target, K, sums, counts, dist_dtype, adopted=spec is not None)
 

@@ -23,6 +23,7 @@ import itertools
 import numpy as np
 
 from .. import backend, codegen
+from ..array.blocks import scatter_updates
 from ..config import FLAGS
 from . import engine
 from .local import CodegenError, Pre, register_lowering
@@ -402,7 +403,6 @@ def _concatenate_join(kind, arrays, axes, fn_kw, target):
   ``b`` shifted by a.shape[axis] along ``axis``: one point-to-point batch."""
   from .. import runtime
   from ..array import extent as ext
-  from .join import _scatter_updates
   ctx = runtime.get()
   axis = fn_kw.get('axis', 0)
   shape = tuple(target.shape)
@@ -417,7 +417,7 @@ def _concatenate_join(kind, arrays, axes, fn_kw, target):
       src = ctx.owner(w)
       t = arr.local[ex].data if src == ctx.rank else None
       updates.append(((ai, tuple(ex.ul)), ext.create(ul, lr, shape), src, t))
-  _scatter_updates(target, updates)
+  scatter_updates(target, updates)
 
 
 def concatenate(a, b, axis=0):

@@ -20,10 +20,10 @@ Routes; every rank issues the same exchanges whether or not it owns tiles:
   * 3-d, every tile spans axes 1 and 2 (batch slabs): each rank runs one
     ``syevj`` per tile it owns; V keeps A's tiling, w (B, n) is cut along axis
     0 at the same places on the same workers; nothing leaves its owner;
-  * 3-d, any other layout: the batch slabs of ``_slabs(arr, 0)`` are each
-    brought to the owner of their first tile by one ``gather_regions``,
-    computed there, and V is delivered into A's tiling by one
-    ``_scatter_updates``; w is tiled by the slabs;
+  * 3-d, any other layout: the batch slabs of ``blocks.gather_slabs(arr, 0)``
+    (``array/blocks.py``, route 3) are computed on their owners, and V is
+    delivered into A's tiling by one ``scatter_slabs``; w is tiled by the
+    slabs;
   * 3-d, replicated: computed on the holder.
 
 ``info`` of every ``syevj`` stays on the device until the end of the
@@ -39,9 +39,8 @@ import numpy as np
 from .. import backend, comm, runtime
 from ..array import distarray
 from ..array import extent as ext
+from ..array.blocks import deferred, gather_slabs, scatter_slabs, spans, whole, with_tiles
 from .base import Expr, as_array
-from .scan import _with_tiles
-from .sort import _like, _slabs
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 
@@ -148,9 +147,8 @@ def _block(t, uplo, infos):
 
 def eigh_array(arr, uplo='L'):
   """(w, V) arrays of the array ``arr``."""
-  from .join import _scatter_updates
   ctx = runtime.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   dt = np.dtype(arr.dtype)
   n = arr.shape[-1]
   infos = []
@@ -159,9 +157,7 @@ def eigh_array(arr, uplo='L'):
     _raise_on_info(infos)
     return distarray.ReplicatedArray(w), distarray.ReplicatedArray(V)
   if arr.ndim == 2:
-    full = ext.from_shape(arr.shape)
-    got = distarray.gather_regions(arr, [(full, r) for r in range(ctx.world_size)])
-    w, V = _block(got[ctx.rank], uplo, infos)  # the same bits on every rank
+    w, V = _block(whole(arr), uplo, infos)  # the same bits on every rank
     _raise_on_info(infos)
     return distarray.ReplicatedArray(w), distarray.ReplicatedArray(V)
   nb = arr.shape[0]
@@ -170,7 +166,7 @@ def eigh_array(arr, uplo='L'):
   def wext(e):
     return ext.create((e.ul[0], 0), (e.lr[0], n), wshape)
 
-  if all(e.ul[1] == 0 and e.lr[1] == n and e.ul[2] == 0 and e.lr[2] == n for e in arr.tiles):
+  if spans(arr, (1, 2)):
     wl, vl = {}, {}
     for e, wk in arr.tiles.items():
       if ctx.is_local(wk):
@@ -178,16 +174,11 @@ def eigh_array(arr, uplo='L'):
     _raise_on_info(infos)
     return (distarray.from_tiles(wshape, dt, {wext(e): wk for e, wk in arr.tiles.items()}, wl),
             distarray.from_tiles(arr.shape, dt, arr.tiles, vl))
-  slabs = _slabs(arr, 0)
-  got = distarray.gather_regions(arr, [(e, ctx.owner(wk)) for e, wk in slabs])
-  target = _like(arr, dt)
-  wl, updates = {}, []
-  for qi, (e, wk) in enumerate(slabs):
-    src = ctx.owner(wk)
-    V = None
-    if src == ctx.rank:
-      wl[wext(e)], V = _block(got[qi], uplo, infos)
-    updates.append(((qi,), e, src, V))
-  _scatter_updates(target, updates)
+  slabs, got = gather_slabs(arr, 0)
+  target = deferred(arr.shape, dt, arr.tiles)
+  wl, vs = {}, {}
+  for qi, t in got.items():
+    wl[wext(slabs[qi][0])], vs[qi] = _block(t, uplo, infos)
+  scatter_slabs(target, slabs, vs)
   _raise_on_info(infos)
   return distarray.from_tiles(wshape, dt, {wext(e): wk for e, wk in slabs}, wl), target

@@ -30,8 +30,8 @@ One node, ``FilterExpr(src, idx)``, with three modes:
             that select nothing are dropped, so the output tiles are uneven.
   mask      ``a[mask]`` / ``compress(axis=None)``: the array is cut into
             slabs along axis 0 at its own tile boundaries; each slab (a view
-            when its tile spans the other axes, else gathered by one
-            ``gather_regions``) meets the matching region of the mask on one
+            when its tile spans the other axes, else gathered: one
+            ``blocks.gather_slabs``) meets the matching region of the mask on one
             owner and is compacted flat into the run [base, base + count) of
             the 1-d result.
 
@@ -54,9 +54,9 @@ import numpy as np
 from .. import backend, comm, runtime
 from ..array import distarray, transfer
 from ..array import extent as ext
+from ..array.blocks import axis_geom, gather_slabs, spans, whole, with_tiles
 from ..util import prod
 from .base import Expr, NotShapeable, as_array
-from .scan import _geom, _with_tiles
 
 
 class FilterExpr(Expr):
@@ -171,18 +171,10 @@ def _empty(shape, dtype):
   return distarray.LocalWrapper(np.empty(tuple(shape), np.dtype(dtype)))
 
 
-def _whole(arr):
-  """The 1-d array ``arr`` as one contiguous device tensor on every rank (one
-  gather_regions), or None if it has no elements."""
-  ctx = runtime.get()
-  be = backend.get()
-  if arr.shape[0] == 0:
-    return None
-  if arr.replicated:
-    return be.contiguous(arr.device_data()).reshape(-1)
-  full = ext.from_shape(arr.shape)
-  got = distarray.gather_regions(arr, [(full, r) for r in range(ctx.world_size)])
-  return be.contiguous(got[ctx.rank]).reshape(-1)
+def _whole_1d(arr):
+  """The 1-d array ``arr`` on every rank (``blocks.whole``), or None if it has
+  no elements."""
+  return whole(arr).reshape(-1) if arr.shape[0] else None
 
 
 def _zeros(shape, tdt):
@@ -221,7 +213,7 @@ def _take_into(buf, e, src, idx, axis, n):
   m = buf.shape[axis]
   oshape = tuple(buf.shape)
   full = lambda d: e.ul[d] == 0 and e.lr[d] == e.array_shape[d]
-  geom = _geom(e.shape, axis)
+  geom = axis_geom(e.shape, axis)
   if all(full(d) for d in range(1, axis)) and all(full(d) for d in range(axis + 2, nd)):
     # the tile's block of every output row is one run of the buffer: write in place
     after = prod(oshape[axis + 1:])
@@ -241,23 +233,23 @@ def take_array(arr, ia, axis):
   import torch
   ctx = runtime.get()
   be = backend.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   backend.spx_dtype(arr.dtype)
   n, m = arr.shape[axis], ia.shape[0]
   oshape = tuple(arr.shape[:axis]) + (m,) + tuple(arr.shape[axis + 1:])
   if prod(oshape) == 0:
     return _empty(oshape, arr.dtype)
-  idx = _whole(ia)
+  idx = _whole_1d(ia)
   tdt = backend.torch_dtype(arr.dtype)
   if arr.replicated:
     out = torch.empty(oshape, dtype=tdt, device=ctx.device)
-    be.take(be.contiguous(arr.device_data()), idx, out, _geom(arr.shape, axis), 0, n)
+    be.take(be.contiguous(arr.device_data()), idx, out, axis_geom(arr.shape, axis), 0, n)
     return distarray.ReplicatedArray(out)
   local = [e for e, w in arr.tiles.items() if ctx.is_local(w)]
   if not local:  # no tile here: the index is range-checked all the same, so every rank raises
     be.take(torch.empty((0,), dtype=tdt, device=ctx.device), idx, torch.empty((m,), dtype=tdt, device=ctx.device),
             (1, 0, 1), 0, n)
-  if all(e.ul[axis] == 0 and e.lr[axis] == n for e in arr.tiles):
+  if spans(arr, (axis,)):
     tiles, out_local = {}, {}
     for e, w in arr.tiles.items():
       oe = ext.create(tuple(0 if d == axis else u for d, u in enumerate(e.ul)),
@@ -265,7 +257,7 @@ def take_array(arr, ia, axis):
       tiles[oe] = w
       if ctx.is_local(w):
         out = torch.empty(oe.shape, dtype=tdt, device=ctx.device)
-        be.take(be.contiguous(arr.fetch(e)), idx, out, _geom(e.shape, axis), 0, n)
+        be.take(be.contiguous(arr.fetch(e)), idx, out, axis_geom(e.shape, axis), 0, n)
         out_local[oe] = out
     return distarray.from_tiles(oshape, arr.dtype, tiles, out_local)
   bdt = _bits_dtype(arr.dtype)
@@ -311,10 +303,10 @@ def compress_array(arr, ca, axis):
   import torch
   ctx = runtime.get()
   be = backend.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   backend.spx_dtype(arr.dtype)
   n = arr.shape[axis]
-  cond = _whole(ca)
+  cond = _whole_1d(ca)
   if _tail_selected(cond, n):
     raise IndexError('compress: the condition of length %d selects past an axis of length %d' % (ca.shape[0], n))
   cond = _fit(cond, n)
@@ -325,7 +317,7 @@ def compress_array(arr, ca, axis):
     if total == 0:
       return _empty(oshape(0), arr.dtype)
     out = torch.empty(oshape(total), dtype=tdt, device=ctx.device)
-    be.compact(be.contiguous(arr.device_data()), cond, out, _geom(arr.shape, axis), ws)
+    be.compact(be.contiguous(arr.device_data()), cond, out, axis_geom(arr.shape, axis), ws)
     return distarray.ReplicatedArray(out)
   cuts = sorted({(e.ul[axis], e.lr[axis]) for e in arr.tiles})
   sid = {lo: s for s, (lo, _) in enumerate(cuts)}
@@ -356,7 +348,7 @@ def compress_array(arr, ca, axis):
     tiles[oe] = w
     if ctx.is_local(w):
       out = torch.empty(oe.shape, dtype=tdt, device=ctx.device)
-      be.compact(be.contiguous(arr.fetch(e)), masks[s], out, _geom(e.shape, axis), wss[s])
+      be.compact(be.contiguous(arr.fetch(e)), masks[s], out, axis_geom(e.shape, axis), wss[s])
       out_local[oe] = out
   return distarray.from_tiles(oshape(total), arr.dtype, tiles, out_local)
 
@@ -365,10 +357,9 @@ def mask_array(arr, ma, flat):
   """``arr[ma]`` (``ma`` of arr's shape) or, with ``flat``, ``np.compress(ma,
   arr)`` for a 1-d ``ma`` over the flattened array."""
   import torch
-  from .sort import _slabs
   ctx = runtime.get()
   be = backend.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   backend.spx_dtype(arr.dtype)
   size = prod(arr.shape)
   tdt = backend.torch_dtype(arr.dtype)
@@ -383,23 +374,15 @@ def mask_array(arr, ma, flat):
       raise IndexError('compress: the condition of length %d selects past the %d elements of the array' % (k, size))
     k = size
   if arr.replicated:
-    if flat:
-      cond = _fit(_whole(ma), size)
-    elif ma.replicated:
-      cond = be.contiguous(ma.device_data()).reshape(-1)
-    else:
-      full = ext.from_shape(ma.shape)
-      cond = be.contiguous(distarray.gather_regions(ma, [(full, r) for r in range(ctx.world_size)])[ctx.rank])
-      cond = cond.reshape(-1)
+    cond = _fit(_whole_1d(ma), size) if flat else whole(ma).reshape(-1)
     total, ws = be.compact_count(cond)
     if total == 0:
       return _empty((0,), arr.dtype)
     out = torch.empty((total,), dtype=tdt, device=ctx.device)
     be.compact(be.contiguous(arr.device_data()).reshape(-1), cond, out, (1, size, 1), ws)
     return distarray.ReplicatedArray(out)
-  slabs = _slabs(arr, 0)
+  slabs, got = gather_slabs(arr, 0)
   row = prod(arr.shape[1:])
-  got = distarray.gather_regions(arr, [(e, ctx.owner(w)) for e, w in slabs])
   if flat:
     # the slab's flat run [a, b) of the condition, as far as the condition reaches
     runs = [(e.ul[0] * row, min(e.lr[0] * row, k)) for e, _ in slabs]

@@ -23,13 +23,15 @@ Join instances follow the reference: for ``map2`` one per tile of
 re-partitioned tile of ``arrays[1]``) pair (``outer_mapper``).  The
 instance's inputs reach the owner of the ``arrays[0]`` tile by one
 ``gather_regions`` exchange per array; yielded pieces travel to the owners
-of the target tiles they overlap by one point-to-point batch and are merged
-there in instance order (tile merge rule, tile.pyx:201-298).
+of the target tiles they overlap by one point-to-point batch
+(``blocks.scatter_updates``) and are merged there in instance order (tile
+merge rule, tile.pyx:201-298).
 """
 import numpy as np
 
-from .. import backend, codegen, comm, runtime
+from .. import backend, codegen, runtime
 from ..array import distarray, extent as ext
+from ..array.blocks import scatter_updates
 from .base import Expr, TupleExpr, as_array
 from .local import CodegenError, LowerEnv, Sym
 
@@ -263,48 +265,4 @@ def run_traced_join(kind, arrays, axes, fn, fn_kw, target):
           t = torch.empty(shape, dtype=backend.torch_dtype(val.dtype), device=ctx.device)
           be.map(val, inputs, t)
       updates.append(((qi, k), tex, src, t))
-  _scatter_updates(target, updates)
-
-
-def _scatter_updates(target, updates):
-  """Deliver every yielded piece to the owners of the target tiles it
-  overlaps and merge them there in instance order.  Collective."""
-  import torch
-  ctx = runtime.get()
-  be = backend.get()
-  tdt = backend.torch_dtype(target.dtype)
-  sends, recvs, merges = [], [], []
-  for order, tex, src, t in updates:
-    if t is not None and t.dtype != tdt:  # pieces travel in the target dtype (the merge casts anyway)
-      conv = torch.empty(t.shape, dtype=tdt, device=t.device)
-      be.copy_region(conv, (0,) * t.dim(), t, (0,) * t.dim(), tuple(t.shape))
-      t = conv
-    if not tex.ndim:
-      pairs = [(tile_ex, tex) for tile_ex in target.tiles]
-    else:
-      pairs = list(ext.find_overlapping(target.tiles, tex))
-    for tile_ex, region in pairs:
-      dst = ctx.owner(target.tiles[tile_ex])
-      if src == ctx.rank:
-        piece = t
-        if tex.ndim and region != tex:
-          rel = tuple(u - o for u, o in zip(region.ul, tex.ul))
-          piece = torch.empty(region.shape, dtype=tdt, device=t.device)
-          be.copy_region(piece, (0,) * region.ndim, t, rel, region.shape)
-        if dst == ctx.rank:
-          merges.append((order, tile_ex, region, piece))
-        else:
-          sends.append((piece, dst))
-      elif dst == ctx.rank:
-        buf = torch.empty(region.shape if region.ndim else (), dtype=tdt, device=ctx.device)
-        recvs.append((buf, src))
-        merges.append((order, tile_ex, region, buf))
-  comm.exchange(sends, recvs)
-  for order, tile_ex, region, piece in sorted(merges, key=lambda m: m[0]):
-    tile = target.local[tile_ex]
-    if not tile.written and region == tile_ex and tuple(region.lr) == tuple(tile_ex.lr) \
-        and piece.is_contiguous() and tuple(piece.shape) == tuple(tile.shape):
-      tile.data = piece  # first write of a whole tile: adopt the piece, no copy
-      tile.written = [tile_ex]
-      continue
-    target.update(region, piece)
+  scatter_updates(target, updates)

@@ -16,7 +16,8 @@ here, for ANY tile layout:
     diagonal tiles).  Two ``gather_regions`` exchanges a step; tiles above the
     diagonal are zero-filled; the result keeps the input's tiling;
   * any other layout is gathered to one owner (it must fit that GPU), factored
-    there and delivered into the input's tiling by one ``_scatter_updates``.
+    there and delivered into the input's tiling by one ``scatter_slabs``
+    (``array/blocks.py``).
 
 ``info`` of every ``potrf`` stays on the device until the end of the
 evaluation: the first failed order over all tiles and ranks is then read once
@@ -24,10 +25,9 @@ and raised as ``np.linalg.LinAlgError``.
 
 ``solve_triangular(L, B, trans)`` solves op(L) X = B for the lower-triangular
 L.  The right-hand-side columns are independent and each needs all of L: L is
-gathered in full to every rank that owns a slab of B, and B takes ``sort``'s
-routes with axis 0 (a tile spanning axis 0 is solved on its owner; otherwise B
-is cut into column slabs, each brought to one owner by one exchange and
-delivered back by one ``_scatter_updates``).
+gathered in full to every rank that owns a slab of B (``blocks.whole``), and B
+takes the three routes of ``array/blocks.py`` with axis 0 (a tile spanning axis
+0 is solved on its owner; otherwise B is cut into column slabs).
 
 Every rank issues the same exchanges whether or not it owns tiles.
 """
@@ -36,9 +36,8 @@ import numpy as np
 from .. import backend, comm, runtime
 from ..array import distarray
 from ..array import extent as ext
+from ..array.blocks import deferred, gather_slabs, map_blocks, scatter_slabs, slabs, whole, with_tiles
 from .base import Expr, as_array
-from .scan import _with_tiles
-from .sort import _like, _slabs
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 _NO_INFO = np.iinfo(np.int64).max
@@ -215,9 +214,8 @@ def _cholesky_tiled(arr, cuts):
 
 
 def cholesky_array(arr):
-  from .join import _scatter_updates
   ctx = runtime.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   _check_square(arr, 'cholesky')
   if arr.replicated:  # held in full by every rank
     L, info = _potrf_block(arr.device_data())
@@ -234,15 +232,13 @@ def cholesky_array(arr):
   cuts = _square_grid(arr)
   if cuts is not None:
     return _cholesky_tiled(arr, cuts)
-  full = ext.from_shape(arr.shape)
-  src = ctx.owner(arr.tiles[min(arr.tiles, key=lambda e: e.ul)])
-  got = distarray.gather_regions(arr, [(full, src)])
-  target = _like(arr, arr.dtype)
-  L, infos = None, []
-  if src == ctx.rank:
-    L, info = _potrf_block(got[0])
+  sl, got = gather_slabs(arr, None)  # the whole matrix on the owner of its first tile
+  target = deferred(arr.shape, arr.dtype, arr.tiles)
+  Ls, infos = {}, []
+  for qi, t in got.items():
+    Ls[qi], info = _potrf_block(t)
     infos.append((0, info))
-  _scatter_updates(target, [((0,), full, src, L)])
+  scatter_slabs(target, sl, Ls)
   _raise_on_info(infos)
   return target
 
@@ -258,37 +254,11 @@ def _solve_block(lfull, t, shape, trans):
 
 
 def solve_triangular_array(L, B, trans):
-  from .join import _scatter_updates
   ctx = runtime.get()
-  be = backend.get()
-  L = _with_tiles(L)
-  B = _with_tiles(B)
-  n = L.shape[0]
-  lfull_ex = ext.from_shape(L.shape)
-
-  def whole_l(ranks):
-    if L.replicated:
-      return be.contiguous(L.device_data())
-    ranks = sorted(ranks)
-    got = distarray.gather_regions(L, [(lfull_ex, r) for r in ranks])
-    return be.contiguous(got[ranks.index(ctx.rank)]) if ctx.rank in ranks else None
-
-  if B.replicated:
-    lfull = whole_l(range(ctx.world_size))
-    return distarray.ReplicatedArray(_solve_block(lfull, B.device_data(), B.shape, trans))
-  if all(e.ul[0] == 0 and e.lr[0] == n for e in B.tiles):
-    lfull = whole_l({ctx.owner(w) for w in B.tiles.values()})
-    out_local = {e: _solve_block(lfull, B.fetch(e), e.shape, trans)
-                 for e, w in B.tiles.items() if ctx.is_local(w)}
-    return distarray.from_tiles(B.shape, B.dtype, B.tiles, out_local)
-  slabs = _slabs(B, 1 if B.ndim == 2 else None)
-  lfull = whole_l({ctx.owner(w) for _e, w in slabs})
-  got = distarray.gather_regions(B, [(e, ctx.owner(w)) for e, w in slabs])
-  target = _like(B, B.dtype)
-  updates = []
-  for qi, (e, w) in enumerate(slabs):
-    src = ctx.owner(w)
-    t = _solve_block(lfull, got[qi], e.shape, trans) if src == ctx.rank else None
-    updates.append(((qi,), e, src, t))
-  _scatter_updates(target, updates)
-  return target
+  L = with_tiles(L)
+  B = with_tiles(B)
+  p = 1 if B.ndim == 2 else None
+  # L to every rank that solves, before B moves: all ranks for a replicated B, else the owners of B's column
+  # slabs (the tiles themselves where every tile spans axis 0)
+  lfull = whole(L, None if B.replicated else {ctx.owner(w) for _e, w in slabs(B, p)})
+  return map_blocks(B, (0,), p, lambda t, shape: _solve_block(lfull, t, shape, trans))

@@ -22,9 +22,9 @@ Routes; every rank issues the same exchanges whether or not it owns tiles:
     n rows is not factored: its rows go on the stack as they are and its rows
     of Q are its rows of the stack's Q);
   * any other layout (tiles cut along axis 1): the row slabs of
-    ``_slabs(arr, 0)`` are each brought to the owner of their first tile by one
-    ``gather_regions``, go through the route above and are delivered into A's
-    tiling by one ``_scatter_updates``.
+    ``blocks.gather_slabs(arr, 0)`` (``array/blocks.py``, route 3) go through
+    the route above and are delivered into A's tiling by one
+    ``scatter_slabs``.
 
 Both results hang off one ``QRExpr`` node: forcing either evaluates the
 factorization once.
@@ -34,9 +34,8 @@ import numpy as np
 from .. import backend, runtime
 from ..array import distarray
 from ..array import extent as ext
+from ..array.blocks import deferred, gather_slabs, scatter_slabs, spans, whole, with_tiles
 from .base import Expr, as_array
-from .scan import _with_tiles
-from .sort import _like, _slabs
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 
@@ -156,10 +155,7 @@ def _tsqr(dtype, n, pieces):
       local[e] = src
     else:
       local[e], handles[t] = be.geqr(src)
-  stack = distarray.from_tiles(stack_shape, dtype, tiles, local)
-  full = ext.from_shape(stack_shape)
-  got = distarray.gather_regions(stack, [(full, r) for r in range(ctx.world_size)])
-  S = be.contiguous(got[ctx.rank])
+  S = whole(distarray.from_tiles(stack_shape, dtype, tiles, local))
   R, top = be.geqr(S)  # the same bits on every rank
   R, D = _nonneg(R)
   seeds = torch.empty(stack_shape, dtype=S.dtype, device=S.device)
@@ -179,9 +175,8 @@ def _tsqr(dtype, n, pieces):
 
 def qr_array(arr):
   """(Q, R) arrays of the array ``arr``."""
-  from .join import _scatter_updates
   ctx = runtime.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   m, n = arr.shape
   dt = np.dtype(arr.dtype)
   if arr.replicated:  # held in full by every rank
@@ -198,18 +193,16 @@ def qr_array(arr):
     # R to every rank: a one-tile array gathered in full
     rt = {ext.from_shape((n, n)): w}
     rarr = distarray.from_tiles((n, n), dt, rt, {k: R for k in rt} if R is not None else {})
-    got = distarray.gather_regions(rarr, [(ext.from_shape((n, n)), r) for r in range(ctx.world_size)])
-    return Q, distarray.ReplicatedArray(got[ctx.rank])
-  if all(e.ul[1] == 0 and e.lr[1] == n for e in arr.tiles):
+    return Q, distarray.ReplicatedArray(whole(rarr))
+  if spans(arr, (1,)):
     order = sorted(arr.tiles, key=lambda e: e.ul[0])
     pieces = [(e.shape[0], arr.tiles[e], arr.fetch(e) if ctx.is_local(arr.tiles[e]) else None) for e in order]
     qs, R = _tsqr(dt, n, pieces)
     Q = distarray.from_tiles(arr.shape, dt, arr.tiles, {order[t]: q for t, q in qs.items()})
     return Q, distarray.ReplicatedArray(R)
-  slabs = _slabs(arr, 0)
-  got = distarray.gather_regions(arr, [(e, ctx.owner(w)) for e, w in slabs])
+  slabs, got = gather_slabs(arr, 0)
   pieces = [(e.shape[0], w, got.get(qi)) for qi, (e, w) in enumerate(slabs)]
   qs, R = _tsqr(dt, n, pieces)
-  target = _like(arr, dt)
-  _scatter_updates(target, [((qi,), e, ctx.owner(w), qs.get(qi)) for qi, (e, w) in enumerate(slabs)])
+  target = deferred(arr.shape, dt, arr.tiles)
+  scatter_slabs(target, slabs, qs)
   return target, distarray.ReplicatedArray(R)

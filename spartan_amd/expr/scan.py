@@ -30,6 +30,7 @@ import numpy as np
 
 from .. import backend, comm, runtime
 from ..array import distarray, transfer
+from ..array.blocks import axis_geom, with_tiles
 from ..util import prod
 from .base import Expr, as_array
 
@@ -85,17 +86,6 @@ def _axis_splits(arr, ax):
   return {ul: i for i, (ul, _) in enumerate(cuts)}
 
 
-def _geom(shape, ax):
-  return prod(shape[:ax]), shape[ax], prod(shape[ax + 1:])
-
-
-def _with_tiles(arr):
-  """``arr`` as an array with device tiles: a host value is distributed."""
-  if isinstance(arr, distarray.LocalWrapper) and not isinstance(arr, distarray.ReplicatedArray):
-    return distarray.from_numpy(np.asarray(arr.value))
-  return arr
-
-
 def _bases_region(ex, ax, tid):
   ul = tuple(tid if d == ax else ex.ul[d] for d in range(ex.ndim))
   shape = tuple(1 if d == ax else ex.shape[d] for d in range(ex.ndim))
@@ -107,7 +97,7 @@ def scan_array(arr, axis):
   import torch
   ctx = runtime.get()
   be = backend.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   if arr.ndim == 0:
     raise ValueError('scan: a 0-d array has no axis to scan')
   odt, adt = backend.scan_dtypes(arr.dtype)
@@ -116,7 +106,7 @@ def scan_array(arr, axis):
   if arr.replicated:  # one tile held in full by every rank
     src = be.contiguous(arr.device_data())
     out = torch.empty(arr.shape, dtype=backend.torch_dtype(odt), device=src.device)
-    be.scan(src, out, (1, prod(arr.shape), 1) if axis is None else _geom(arr.shape, ax))
+    be.scan(src, out, (1, prod(arr.shape), 1) if axis is None else axis_geom(arr.shape, ax))
     return distarray.ReplicatedArray(out)
   tids = _axis_splits(arr, ax)
   T = len(tids)
@@ -129,17 +119,17 @@ def scan_array(arr, axis):
     tot = torch.empty(tshape, dtype=tadt, device=ctx.device)
     be.fill(tot, backend.FILL_CONST, 0, 0, 0, (0,) * nd, tshape)
     for ex in local:
-      o, n, i = _geom(ex.shape, ax)
+      o, n, i = axis_geom(ex.shape, ax)
       part = torch.empty((o, i), dtype=tadt, device=ctx.device)
       be.scan(data[ex], None, (o, n, i), totals=part)
       ul, shape = _bases_region(ex, ax, tids[ex.ul[ax]])
       be.copy_region(tot, ul, part.reshape(shape), (0,) * nd, shape)
     comm.all_reduce(tot, 'sum')
     bases = torch.empty(tshape, dtype=tadt, device=ctx.device)
-    be.scan(tot, bases, (1, prod(tshape), 1) if axis is None else _geom(tshape, ax), exclusive=True)
+    be.scan(tot, bases, (1, prod(tshape), 1) if axis is None else axis_geom(tshape, ax), exclusive=True)
   out_local = {}
   for ex in local:
-    o, n, i = _geom(ex.shape, ax)
+    o, n, i = axis_geom(ex.shape, ax)
     carry = None
     if bases is not None:
       ul, shape = _bases_region(ex, ax, tids[ex.ul[ax]])
@@ -157,7 +147,7 @@ def scan_array_host(arr, reduce_fn, scan_fn, axis):
   tiles: reduce_fn(tile, axis), scan_fn over the totals, tile[first] += base,
   scan_fn(tile, axis), upload (scan.py:24-64, :83-96)."""
   ctx = runtime.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   if arr.replicated:
     arr = distarray.from_numpy(arr.glom())
   nd = arr.ndim

@@ -9,15 +9,12 @@ contract here is NumPy's result for ANY tile layout -- ``np.sort(a, axis)``
 and ``np.argsort(a, axis, kind='stable')``, NaNs last, ``-0.0 == +0.0``.
 
 A line has to be in one place to be sorted (``spx_sort``: LDS bitonic sort
-for short lines, radix passes for long ones), so for an integer axis
-
-  * a tile that spans the whole axis is sorted on its owner, no exchange (the
-    common case: row tiles sorted along axis 1);
-  * otherwise the array is cut into slabs along ``p = largest_dim_axis(shape,
-    exclude_axes=[axis])`` at the array's own cuts along p; each slab,
-    complete along ``axis``, is brought to one owner by ONE ``gather_regions``
-    exchange, sorted there and delivered to the target's tiles by one
-    ``_scatter_updates`` batch.  The target keeps the input's tile layout.
+for short lines, radix passes for long ones), so an integer axis takes the
+three routes of ``array/blocks.py`` (``map_blocks``): a tile that spans the
+whole axis is sorted on its owner, no exchange (the common case: row tiles
+sorted along axis 1); otherwise the slabs are cut along ``p =
+largest_dim_axis(shape, exclude_axes=[axis])`` and the target keeps the
+input's tile layout.
 
 A 1-d array in several tiles has no other axis to cut: it is gathered whole
 to one owner, so it must fit in that GPU's memory next to the sort's
@@ -34,13 +31,12 @@ satisfies NumPy's partition contract; ``kth`` is range-checked only.
 """
 import numpy as np
 
-from .. import backend, runtime
+from .. import backend
 from ..array import distarray
 from ..array import extent as ext
-from ..array.tile import Tile
+from ..array.blocks import axis_geom, gather_slabs, map_blocks, scatter_slabs, with_tiles
 from ..util import prod
 from .base import Expr, as_array
-from .scan import _geom, _with_tiles
 
 
 class SortExpr(Expr):
@@ -117,70 +113,27 @@ def _sort_block(t, shape, ax, want_idx):
   src = be.contiguous(t)
   odt = np.int64 if want_idx else backend.np_dtype(src.dtype)
   out = torch.empty(tuple(shape), dtype=backend.torch_dtype(odt), device=src.device)
-  be.sort(src, None if want_idx else out, out if want_idx else None, _geom(shape, ax))
+  be.sort(src, None if want_idx else out, out if want_idx else None, axis_geom(shape, ax))
   return out
-
-
-def _slabs(arr, p):
-  """The array cut along axis p at every tile boundary along p:
-  [(extent, worker of the first tile it overlaps)] in order."""
-  if p is None:
-    full = ext.from_shape(arr.shape)
-    return [(full, arr.tiles[min(arr.tiles, key=lambda e: e.ul)])]
-  bounds = sorted({e.ul[p] for e in arr.tiles} | {e.lr[p] for e in arr.tiles})
-  tiles = sorted(arr.tiles.items(), key=lambda kv: kv[0].ul)
-  out = []
-  for lo, hi in zip(bounds, bounds[1:]):
-    ul = tuple(lo if d == p else 0 for d in range(arr.ndim))
-    lr = tuple(hi if d == p else arr.shape[d] for d in range(arr.ndim))
-    w = next(w for e, w in tiles if e.ul[p] <= lo < e.lr[p])
-    out.append((ext.create(ul, lr, arr.shape), w))
-  return out
-
-
-def _like(arr, dtype):
-  """Unwritten array with arr's shape and tile layout."""
-  ctx = runtime.get()
-  tdt = backend.torch_dtype(dtype)
-  local = {ex: Tile.deferred(ex.shape, tdt, ctx.device, ex) for ex, w in arr.tiles.items() if ctx.is_local(w)}
-  return distarray.DistArrayImpl(arr.shape, dtype, dict(arr.tiles), local)
 
 
 def sort_array(arr, axis, want_idx):
-  from .join import _scatter_updates
-  ctx = runtime.get()
   be = backend.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   if arr.ndim == 0:
     raise ValueError('sort: a 0-d array has no axis to sort')
   odt = np.dtype(np.int64) if want_idx else np.dtype(arr.dtype)
   backend.spx_dtype(arr.dtype)
   size = prod(arr.shape)
-  if arr.replicated:  # one tile held in full by every rank
-    shape = (size,) if axis is None else arr.shape
-    return distarray.ReplicatedArray(_sort_block(arr.device_data(), shape, 0 if axis is None else axis, want_idx))
-  if size == 0:
+  if size == 0 and not arr.replicated:
     return distarray.create((0,) if axis is None else arr.shape, odt)
-  if axis is None:
-    full = ext.from_shape(arr.shape)
-    src = ctx.owner(arr.tiles[min(arr.tiles, key=lambda e: e.ul)])
-    got = distarray.gather_regions(arr, [(full, src)])
-    target = distarray.create((size,), odt)
-    t = _sort_block(be.contiguous(got[0]).reshape(-1), (size,), 0, False) if src == ctx.rank else None
-    _scatter_updates(target, [((0,), ext.from_shape((size,)), src, t)])
-    return target
-  if all(e.ul[axis] == 0 and e.lr[axis] == arr.shape[axis] for e in arr.tiles):
-    out_local = {e: _sort_block(arr.fetch(e), e.shape, axis, want_idx)
-                 for e, w in arr.tiles.items() if ctx.is_local(w)}
-    return distarray.from_tiles(arr.shape, odt, arr.tiles, out_local)
-  p = ext.largest_dim_axis(arr.shape, exclude_axes=[axis]) if arr.ndim > 1 else None
-  slabs = _slabs(arr, p)
-  got = distarray.gather_regions(arr, [(e, ctx.owner(w)) for e, w in slabs])
-  target = _like(arr, odt)
-  updates = []
-  for qi, (e, w) in enumerate(slabs):
-    src = ctx.owner(w)
-    t = _sort_block(got[qi], e.shape, axis, want_idx) if src == ctx.rank else None
-    updates.append(((qi,), e, src, t))
-  _scatter_updates(target, updates)
+  if axis is not None:
+    p = ext.largest_dim_axis(arr.shape, exclude_axes=[axis]) if arr.ndim > 1 else None
+    return map_blocks(arr, (axis,), p, lambda t, shape: _sort_block(t, shape, axis, want_idx), dtype=odt)
+  if arr.replicated:  # one tile held in full by every rank
+    return distarray.ReplicatedArray(_sort_block(arr.device_data(), (size,), 0, want_idx))
+  slabs, got = gather_slabs(arr, None)
+  target = distarray.create((size,), odt)
+  flat = {qi: _sort_block(be.contiguous(t).reshape(-1), (size,), 0, False) for qi, t in got.items()}
+  scatter_slabs(target, slabs, flat, lambda e: ext.from_shape((size,)))
   return target

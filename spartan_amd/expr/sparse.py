@@ -8,8 +8,9 @@ of CSR, array/sparse.py); the class mixin ``SparseExpr`` marks it.  What may
 be done with one:
 
   * ``dot(S, X)``, X dense (n,), (n, 1) or (n, p): X is brought in full to
-    every rank by ONE ``gather_regions`` (every rank issues it, with or without
-    slabs), then each rank runs ``csrmm`` on each of its slabs.  The result is
+    every rank by ``blocks.whole`` (one ``gather_regions``; every rank issues
+    it, with or without slabs), then each rank runs ``csrmm`` on each of its
+    slabs.  The result is
     dense, in row slabs aligned with S's on the same workers; no cross-rank
     reduction.  One ``g`` (lanes per row) is taken from the whole matrix's
     plan and given to every slab, so a row's bits do not depend on the layout;
@@ -29,6 +30,7 @@ from .. import backend, runtime
 from ..array import distarray
 from ..array import extent as ext
 from ..array import sparse as sparray
+from ..array.blocks import whole
 from ..array.sparse import TODENSE
 from .base import Expr, Val
 
@@ -231,9 +233,7 @@ def sparse_dot(S, x):
   dt = np.dtype(np.result_type(S.dtype, x.dtype))
   if dt not in _FLOATS:
     raise TypeError('dot(sparse, dense): result dtype %s is not float32 / float64' % dt)
-  full = ext.from_shape(xs)
-  got = distarray.gather_regions(x, [(full, r) for r in range(ctx.world_size)])
-  X = be.contiguous(got[ctx.rank], dt).reshape(n, p)
+  X = be.contiguous(whole(x), dt).reshape(n, p)
   Sd = S.astype(dt)
   g = backend.csrmm_plan(dt, m, S.nnz, p)[0]  # one g for every slab: the layout does not change a row's bits
   tiles, local = {}, {}

@@ -32,17 +32,15 @@ returns a constant array: the intent is restated, not the stub.  Every window
 holds its first element, so there is no fill value (no -1e12); NaN propagates
 as in ``np.maximum``.
 
-Tiles.  Both need whole (W, H) planes -- stencil all C of them -- in one place:
+Tiles.  Both need whole (W, H) planes -- stencil all C of them -- in one
+place, by the three routes of ``array/blocks.py`` (``map_blocks``):
 
   * every tile spans (C, W, H) (images dealt along axis 0, the benchmark's
     layout): each tile is convolved / pooled on its owner, the output keeps
     the input's cuts along axis 0 and no array data moves;
-  * any other layout (the reference's tests tile the two spatial axes): the
-    array is cut into slabs along axis 0 at its tile boundaries, each slab is
-    brought to one owner by one ``gather_regions``, computed there and
-    delivered by ``_scatter_updates`` into a target tiled along axis 0 at the
-    same cuts.  Every rank issues the same collectives whether or not it owns
-    tiles.  Limit: one slab and its output must fit on one GPU (a halo
+  * any other layout (the reference's tests tile the two spatial axes): slabs
+    along axis 0, delivered into a target tiled along axis 0 at the same
+    cuts.  Limit: one slab and its output must fit on one GPU (a halo
     exchange between spatial tiles is the follow-up);
   * a replicated / host input gives a replicated result.
 
@@ -52,10 +50,10 @@ without elements gives a host array of the result's shape.
 """
 import numpy as np
 
-from .. import backend, runtime
+from .. import backend
 from ..array import distarray
 from ..array import extent as ext
-from ..array.tile import Tile
+from ..array.blocks import deferred, map_blocks, whole
 from ..util import prod
 from .base import Expr, as_array
 
@@ -139,46 +137,16 @@ def maxpool(images, pool_size=2, stride=2):
 
 
 # ------------------------------------------------------------- evaluation
-def _whole(arr):
-  """``arr`` as one contiguous device tensor on every rank (one gather_regions)."""
-  ctx = runtime.get()
-  be = backend.get()
-  if arr.replicated:
-    return be.contiguous(arr.device_data())
-  full = ext.from_shape(arr.shape)
-  got = distarray.gather_regions(arr, [(full, r) for r in range(ctx.world_size)])
-  return be.contiguous(got[ctx.rank])
-
-
 def _planes(arr, oshape, block):
-  """``block(t)`` -- (n, C, W, H) device block -> (n,) + oshape[1:] -- over
-  ``arr`` along axis 0, by the three routes of the module docstring."""
-  from .join import _scatter_updates
-  from .sort import _slabs
-  ctx = runtime.get()
+  """``block(t)`` -- (n, C, W, H) contiguous device block -> (n,) + oshape[1:]
+  -- over ``arr`` along axis 0, by the three routes of the module docstring."""
   be = backend.get()
   oshape = tuple(int(s) for s in oshape)
   if prod(arr.shape) == 0 or prod(oshape) == 0:
     return distarray.LocalWrapper(np.empty(oshape, np.dtype(arr.dtype)))
-  if arr.replicated:  # a host value or a replicated device array: every rank computes the whole
-    return distarray.ReplicatedArray(block(be.contiguous(arr.device_data())))
   out_ex = lambda e: ext.create((e.ul[0], 0, 0, 0), (e.lr[0],) + oshape[1:], oshape)
-  if all(e.ul[d] == 0 and e.lr[d] == arr.shape[d] for e in arr.tiles for d in (1, 2, 3)):
-    tiles = {out_ex(e): w for e, w in arr.tiles.items()}
-    out_local = {out_ex(e): block(be.contiguous(arr.fetch(e))) for e, w in arr.tiles.items() if ctx.is_local(w)}
-    return distarray.from_tiles(oshape, arr.dtype, tiles, out_local)
-  slabs = _slabs(arr, 0)
-  got = distarray.gather_regions(arr, [(e, ctx.owner(w)) for e, w in slabs])
-  tiles = {out_ex(e): w for e, w in slabs}
-  tdt = backend.torch_dtype(arr.dtype)
-  local = {oe: Tile.deferred(oe.shape, tdt, ctx.device, oe) for oe, w in tiles.items() if ctx.is_local(w)}
-  target = distarray.DistArrayImpl(oshape, np.dtype(arr.dtype), tiles, local)
-  updates = []
-  for qi, (e, w) in enumerate(slabs):
-    src = ctx.owner(w)
-    updates.append(((qi,), out_ex(e), src, block(be.contiguous(got[qi])) if src == ctx.rank else None))
-  _scatter_updates(target, updates)
-  return target
+  return map_blocks(arr, (1, 2, 3), 0, lambda t, shape: block(be.contiguous(t)), out_shape=oshape, out_extent=out_ex,
+                    target=lambda slabs: deferred(oshape, arr.dtype, {out_ex(e): w for e, w in slabs}))
 
 
 def stencil_array(images, filters):
@@ -186,7 +154,7 @@ def stencil_array(images, filters):
   be = backend.get()
   n, c, w, h = images.shape
   f = filters.shape[0]
-  flt = _whole(filters)  # a collective: before any early return that depends on the images' layout only
+  flt = whole(filters)  # a collective: before any early return that depends on the images' layout only
 
   def block(t):
     out = torch.empty((t.shape[0], f, w, h), dtype=t.dtype, device=t.device)

@@ -14,12 +14,9 @@ unsupervised.py).  The contract here, for a line ``x`` of length n and
     ``np.argsort(~x, kind='stable')[:k]`` for integers and bool.
 
 The result has the input's shape with ``axis`` replaced by ``k``.  A line has
-to be in one place to be selected from, so the routes are ``sort_array``'s: a
-tile that spans the axis is selected on its owner with no exchange; otherwise
-the array is cut into slabs along another axis, each slab brought to one owner
-by one ``gather_regions`` exchange, selected there and delivered by one
-``_scatter_updates`` batch; a replicated array is selected in place.  Every
-rank issues the same exchanges.
+to be in one place to be selected from, so the routes are ``sort_array``'s,
+the three of ``array/blocks.py``; route 3 delivers into a fresh array of the
+result's shape in the default layout.  Every rank issues the same exchanges.
 
 ``k`` above ``backend.TOPK_K_MAX`` (the candidates of a line are ordered by
 one LDS sort): ``largest=False`` goes through ``sort`` / ``argsort`` and a
@@ -27,13 +24,13 @@ slice; ``largest=True`` raises ``NotImplementedError``.
 """
 import numpy as np
 
-from .. import backend, runtime
+from .. import backend
 from ..array import distarray
 from ..array import extent as ext
+from ..array.blocks import axis_geom, map_blocks, with_tiles
 from ..util import prod
 from .base import Expr, as_array
-from .scan import _geom, _with_tiles
-from .sort import _slabs, argsort, sort
+from .sort import argsort, sort
 
 
 class TopkExpr(Expr):
@@ -104,7 +101,7 @@ def _topk_block(t, shape, ax, k, largest, want_idx):
   src = be.contiguous(t)
   odt = np.int64 if want_idx else backend.np_dtype(src.dtype)
   out = torch.empty(_out_shape(shape, ax, k), dtype=backend.torch_dtype(odt), device=src.device)
-  be.topk(src, None, None if want_idx else out, out if want_idx else None, _geom(shape, ax), k, largest)
+  be.topk(src, None, None if want_idx else out, out if want_idx else None, axis_geom(shape, ax), k, largest)
   return out
 
 
@@ -115,31 +112,15 @@ def _out_extent(e, ax, k, out_shape):
 
 
 def topk_array(arr, k, axis, largest, want_idx):
-  from .join import _scatter_updates
-  ctx = runtime.get()
-  arr = _with_tiles(arr)
+  arr = with_tiles(arr)
   if arr.ndim == 0:
     raise ValueError('topk: a 0-d array has no axis to select along')
   odt = np.dtype(np.int64) if want_idx else np.dtype(arr.dtype)
   backend.spx_dtype(arr.dtype)
   out_shape = _out_shape(arr.shape, axis, k)
-  if arr.replicated:  # one tile held in full by every rank
-    return distarray.ReplicatedArray(_topk_block(arr.device_data(), arr.shape, axis, k, largest, want_idx))
-  if prod(out_shape) == 0:
+  if prod(out_shape) == 0 and not arr.replicated:
     return distarray.create(out_shape, odt)
-  if all(e.ul[axis] == 0 and e.lr[axis] == arr.shape[axis] for e in arr.tiles):
-    tiles = {_out_extent(e, axis, k, out_shape): w for e, w in arr.tiles.items()}
-    out_local = {_out_extent(e, axis, k, out_shape): _topk_block(arr.fetch(e), e.shape, axis, k, largest, want_idx)
-                 for e, w in arr.tiles.items() if ctx.is_local(w)}
-    return distarray.from_tiles(out_shape, odt, tiles, out_local)
   p = ext.largest_dim_axis(arr.shape, exclude_axes=[axis]) if arr.ndim > 1 else None
-  slabs = _slabs(arr, p)
-  got = distarray.gather_regions(arr, [(e, ctx.owner(w)) for e, w in slabs])
-  target = distarray.create(out_shape, odt)
-  updates = []
-  for qi, (e, w) in enumerate(slabs):
-    src = ctx.owner(w)
-    t = _topk_block(got[qi], e.shape, axis, k, largest, want_idx) if src == ctx.rank else None
-    updates.append(((qi,), _out_extent(e, axis, k, out_shape), src, t))
-  _scatter_updates(target, updates)
-  return target
+  return map_blocks(arr, (axis,), p, lambda t, shape: _topk_block(t, shape, axis, k, largest, want_idx),
+                    out_shape=out_shape, out_extent=lambda e: _out_extent(e, axis, k, out_shape), dtype=odt,
+                    target=lambda slabs: distarray.create(out_shape, odt))

@@ -12,7 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import spartan_amd  # noqa: E402
 from spartan_amd import backend, expr  # noqa: E402
-from spartan_amd.array import distarray, extent as ext, transfer  # noqa: E402
+from spartan_amd.array import blocks, distarray, extent as ext, transfer  # noqa: E402
 from spartan_amd.expr import base as ebase, join as ejoin  # noqa: E402
 from spartan_amd.examples import kmeans as km  # noqa: E402
 
@@ -45,7 +45,7 @@ def main():
                            (expr, 'outer', 'outer'), (expr, 'argmin', 'argmin'), (expr, 'map2', 'map2'),
                            (km, '_replicated_f64', '_replicated_f64'), (km, '_row_blocks', '_row_blocks'),
                            (km, '_assign_fused', '_assign_fused'), (km, '_center_join', '_center_join'),
-                           (km, '_count_join', '_count_join'), (ejoin, '_scatter_updates', '_scatter_updates'),
+                           (km, '_count_join', '_count_join'), (blocks, 'scatter_updates', 'scatter_updates'),
                            (transfer, 'download', 'download'), (transfer, 'upload', 'upload'),
                            (km, '_step_domain', '_step_domain'), (km, '_fused_step', '_fused_step'),
                            (km, '_deliver_full', '_deliver_full'), (torch, 'empty', 'torch.empty')):
