@@ -433,6 +433,12 @@ class HipBackend:
     """Fused map+reduce over one tile -> the tile's partial, a device tensor of
     out_shape and out_dtype; for argmin/argmax a (values, int64 indices) pair."""
     import torch
+    if np.dtype(out_dtype) not in binding._DT:
+      # int8 / uint8 / int16 results: the finalize pass knows no such type, so
+      # reduce into the type's accumulator (int32, sums int64) and narrow that
+      # with the identity-cast map (wraps like astype)
+      wide = self.reduce(root, op, inputs, in_shape, axis, out_shape, codegen.acc_dtype(op, out_dtype), idx_geom)
+      return self.contiguous(wide, out_dtype)
     slots = sorted(inputs)
     # launch plan of an identical call (same IR signature, operand layouts and
     # shapes: an iterative driver's replayed DAG): the view, the plan

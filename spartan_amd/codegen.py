@@ -619,18 +619,16 @@ REDOPS = ('sum', 'min', 'max', 'argmin', 'argmax')
 
 
 def acc_dtype(op, dt):
+  """Accumulator dtype of a reduction over values of ``dt``: int64 for integer
+  and bool sums; for min / max / arg ops the value type, bools as int64 and
+  int8 / uint8 / int16 as int32 (the lane combines -- shfl_xor, dpp_mov --
+  move whole dwords; every value of the three fits int32, so the order and
+  the extremes are the value type's own)."""
   dt = np.dtype(dt)
-  if op == 'sum':
-    if dt.kind in 'biu':
-      return np.dtype(np.int64)
-    return dt
-  if op in ('min', 'max'):
-    if dt.kind == 'b':
-      return np.dtype(np.int64)
-    return dt
-  # arg ops keep the value type
-  if dt.kind == 'b':
+  if dt.kind == 'b' or (op == 'sum' and dt.kind in 'iu'):
     return np.dtype(np.int64)
+  if dt.kind in 'iu' and dt.itemsize < 4:
+    return np.dtype(np.int32)
   return dt
 
 

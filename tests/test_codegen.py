@@ -74,6 +74,26 @@ def test_reduce_source_has_one_entry(kind, op):
   assert codegen.named(src, 'spx_reduce', kind)[1].startswith('spx_reduce_%s_' % kind)
 
 
+_REDUCE_DTYPES = sorted((np.dtype('bool' if k == '?' else k) for k in codegen.CTYPE), key=lambda d: d.str)
+
+
+@pytest.mark.parametrize('kind', ['rows', 'rowsp', 'cols'])
+@pytest.mark.parametrize('dt', _REDUCE_DTYPES, ids=lambda d: d.name)
+def test_reduce_compile_matrix(dt, kind):
+  """Every (dtype, op, skeleton) of gen_reduce over a bare In(0, dt), every
+  dtype CTYPE lowers: the vector width is the planner's (input and accumulator
+  item sizes), the accumulator acc_dtype's.  int8 / uint8 / int16 min / max /
+  arg ops accumulate in int32: the lane combines move whole dwords."""
+  for op in codegen.REDOPS:
+    adt = codegen.acc_dtype(op, dt)
+    assert adt.itemsize in (4, 8), (op, dt, adt)
+    if op == 'sum':
+      assert adt == (dt if dt.kind == 'f' else I64)
+    elif dt.kind in 'iu':
+      assert adt == (I32 if dt.itemsize < 4 else dt)
+    _compile(codegen.gen_reduce(In(0, dt), [(0, dt)], ['c'], kind, op, codegen.vec_width([dt, adt])))
+
+
 @pytest.mark.parametrize('dt', [F32, F64])
 def test_rowdot_cols_compile(dt):
   """DotReduceFusion's row-dot leaf in the column-reduce skeleton (vector and
