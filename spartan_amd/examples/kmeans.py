@@ -36,7 +36,7 @@ import weakref
 import numpy as np
 
 from .. import backend, comm, expr, runtime
-from ..array import blocks, distarray, extent as ext, transfer
+from ..array import blocks, combine, distarray, extent as ext, transfer
 from ..expr.join import register_argmin_fusion, register_join
 
 
@@ -107,24 +107,6 @@ def _local_rows(X, ncols):
   return blocks, ((qi, region, p if p.stride(-1) == 1 else be.contiguous(p)) for qi, region, p in mine)
 
 
-def _deliver_full(target, full):
-  """Copy a full-size tensor, identical on every rank, into target's local
-  tiles; a local tile that IS the whole array and was never written adopts
-  the tensor instead (no copy: the join made it for this target alone)."""
-  from ..expr.engine import _copy_out
-  be = backend.get()
-  if len(target.local) == 1:
-    (d, t), = target.local.items()
-    if (not t.written and tuple(d.ul) == (0,) * len(target.shape) and tuple(d.shape) == tuple(target.shape)
-        and tuple(full.shape) == tuple(d.shape) and full.dtype == backend.torch_dtype(target.dtype)
-        and full.is_contiguous()):
-      t.data = full
-      t.written = [d]
-      return
-  for d, t in target.local.items():
-    _copy_out(be, t, full, d)
-
-
 def _dist_join(kind, arrays, axes, fn_kw, target):
   import torch
   if kind != 'outer' or tuple(axes) != (0, 0) or len(arrays[0].shape) != 2:
@@ -152,7 +134,7 @@ def _count_join(kind, arrays, axes, fn_kw, target):
   pre = _PIPE.take(labels, K)
   if pre is not None:
     comm.all_reduce(pre, 'sum')
-    _deliver_full(target, pre)
+    combine.deliver(target, pre)
     _PIPE.counts_delivered(target)
     return
   counts = torch.zeros((K,), dtype=torch.int64, device=ctx.device)
@@ -160,7 +142,7 @@ def _count_join(kind, arrays, axes, fn_kw, target):
     lab = be.contiguous(tile.data, np.int64).reshape(-1)
     be.bincount(lab, counts, zero_first=False)
   comm.all_reduce(counts, 'sum')
-  _deliver_full(target, counts)
+  combine.deliver(target, counts)
 
 
 def _center_join(kind, arrays, axes, fn_kw, target):
@@ -173,7 +155,7 @@ def _center_join(kind, arrays, axes, fn_kw, target):
   pre = _PIPE.take(labels, K, X)
   if pre is not None:  # the fused step of this labels array already summed X
     comm.all_reduce(pre, 'sum')
-    _deliver_full(target, pre)
+    combine.deliver(target, pre)
     _PIPE.sums_delivered(X, K, target)
     return
   sums = torch.zeros((K, D), dtype=torch.float64, device=ctx.device)
@@ -187,7 +169,7 @@ def _center_join(kind, arrays, axes, fn_kw, target):
     lab = be.contiguous(lab_blocks[qi], np.int64).reshape(-1)
     be.kmeans_accumulate(pts, lab, sums, counts, zero_first=False)
   comm.all_reduce(sums, 'sum')
-  _deliver_full(target, sums)
+  combine.deliver(target, sums)
 
 
 def _step_domain(X, K):

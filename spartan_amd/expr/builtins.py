@@ -348,7 +348,7 @@ def _bincount_mapper(ex, tiles, minlength=None):
 def _bincount_join(kind, arrays, axes, fn_kw, target):
   import torch
   from .. import comm, runtime
-  from ..examples.kmeans import _deliver_full
+  from ..array import combine
   ctx = runtime.get()
   be = backend.get()
   K = target.shape[0]
@@ -373,7 +373,7 @@ def _bincount_join(kind, arrays, axes, fn_kw, target):
         wt = be.contiguous(wt, np.float64)
       be.kmeans_accumulate(be.contiguous(wt).reshape(-1, 1), lab, acc, counts, zero_first=False)
   comm.all_reduce(acc, 'sum')
-  _deliver_full(target, acc.reshape(K))
+  combine.deliver(target, acc.reshape(K))
 
 
 def bincount(v, weights=None, minlength=None):

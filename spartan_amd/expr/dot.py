@@ -23,7 +23,7 @@ import numpy as np
 
 from .. import backend, comm, runtime
 from ..config import FLAGS
-from ..array import distarray, extent as ext
+from ..array import combine, distarray, extent as ext
 from ..array.distarray import LocalWrapper
 from .base import Expr, as_array
 
@@ -176,8 +176,7 @@ def run_dot(a, b, tile_hint=None):
         ct = torch.empty((ex2.shape[0], N), dtype=backend.torch_dtype(dtype), device=ctx.device)
         be.gemm(at, be.contiguous(bk), ct, 1.0, 0.0)
         partials[ex2] = ct
-    return _combine_rows(partials, A, M, N, out_shape, dtype, tile_hint, k_split=any(
-        ex.ul[1] != 0 or ex.lr[1] != K for ex in A.tiles2()))
+    return _combine_rows(partials, A, M, N, out_shape, dtype, tile_hint)
   btiles = B.tiles2() if not b.replicated else {ext.from_shape((K, N)): -1}
   # no zero fill of the (M, N) partial: the first GEMM into each column
   # block runs with beta = 0, and only column blocks this rank computes
@@ -220,7 +219,7 @@ def run_dot(a, b, tile_hint=None):
   for c0, c1 in col_blocks:
     if (c0, c1) not in started:
       C[:, c0:c1].zero_()
-  _scatter_full(output, C.reshape(out_shape), 'sum')
+  combine.across_ranks(output, C.reshape(out_shape), 'sum')
   return output
 
 
@@ -247,8 +246,7 @@ def _blocks_disjoint(col_blocks):
 
 
 def _owner_slabs(output, ctx, M):
-  from .engine import _rank_slabs
-  return _rank_slabs(output, ctx) and M % ctx.world_size == 0
+  return combine.rank_slabs(output) and M % ctx.world_size == 0
 
 
 # slab gathers in flight ahead of the GEMM that consumes them (_dot_overlapped)
@@ -323,56 +321,12 @@ def _dot_overlapped(output, a, A, plan, b, B, K, M, N, dtype, C, col_blocks):
   return output
 
 
-def _scatter_full(output, full, op):
-  """Sum the per-rank full buffers and deliver each output tile to its owner."""
-  from .engine import _copy_out, _rank_slabs
-  ctx = runtime.get()
-  be = backend.get()
-  if not ctx.distributed and len(output.local) == 1:
-    (d, t), = output.local.items()
-    if tuple(d.ul) == (0,) * len(output.shape) and tuple(t.shape) == tuple(output.shape):
-      t.data = full.reshape(t.shape) if full.is_contiguous() else full.contiguous().reshape(t.shape)
-      t.written = [d]
-      return
-  if ctx.distributed:
-    if _rank_slabs(output, ctx):
-      from .engine import COMBINE_CALLS
-      COMBINE_CALLS['reduce_scatter'] += 1
-      (d, t), = output.local.items()
-      comm.reduce_scatter_rows(t.data, full.contiguous(), op)
-      t.written = [d]
-      return
-    comm.all_reduce(full, op)
-  for d, t in output.local.items():
-    _copy_out(be, t, full.contiguous(), d)
-
-
-def _combine_rows(partials, A, M, N, out_shape, dtype, tile_hint, k_split):
-  """Row-block partials {A extent: (rows, N) tensor} -> output DistArray."""
-  import torch
-  ctx = runtime.get()
-  be = backend.get()
+def _combine_rows(partials, A, M, N, out_shape, dtype, tile_hint):
+  """Row-block partials {A extent: (rows, N) tensor} -> output DistArray (a K
+  split lands several partials on the same rows: they are summed)."""
   output = distarray.create(out_shape, dtype, reducer=np.add, tile_hint=tile_hint)
   two_d = len(out_shape) == 2
-  # aligned: every A row block is exactly an output tile of the same rank, no K split
-  aligned = not k_split
-  if aligned:
-    for ex2, w in A.tiles2().items():
-      d = ext.create((ex2.ul[0], 0), (ex2.lr[0], N), (M, N)) if two_d else \
-          ext.create((ex2.ul[0],), (ex2.lr[0],), out_shape)
-      if d not in output.tiles or ctx.owner(output.tiles[d]) != ctx.owner(w):
-        aligned = False
-        break
-  if aligned:
-    for ex2, ct in partials.items():
-      d = ext.create((ex2.ul[0], 0), (ex2.lr[0], N), (M, N)) if two_d else \
-          ext.create((ex2.ul[0],), (ex2.lr[0],), out_shape)
-      t = output.local[d]
-      t.data = ct.reshape(t.shape)
-      t.written = [d]
-    return output
-  full = torch.zeros((M, N), dtype=backend.torch_dtype(dtype), device=ctx.device)
-  for ex2, ct in partials.items():
-    be.merge(full, None, (ex2.ul[0], 0), ct, 'sum', fastpath=False)
-  _scatter_full(output, full.reshape(out_shape), 'sum')
+  combine.land(output, [(ext.create((ex2.ul[0], 0), (ex2.lr[0], N), (M, N)) if two_d else
+                         ext.create((ex2.ul[0],), (ex2.lr[0],), out_shape), w, partials.get(ex2))
+                        for ex2, w in A.tiles2().items()], 'sum')
   return output

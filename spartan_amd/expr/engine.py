@@ -11,18 +11,18 @@ DistArray.update + tile.merge for the partials) is done here per rank:
     collective ``gather_regions`` (row-strip co-tiled inputs need none);
  3. lower the LocalExpr tree once and launch ONE generated kernel per local
     tile (map, or fused map+reduce);
- 4. for reductions, combine the tile partials: written straight into the
-    output tile when the partial lands exactly on a tile of the same rank,
-    otherwise merged locally and combined across ranks with RCCL
+ 4. for reductions, hand the tile partials to ``array.combine.land``: adopted
+    as the output tile when the partial lands exactly on a tile of the same
+    rank, otherwise merged locally and combined across ranks with RCCL
     (reduce_scatter / all_reduce; all_gather + spx_argreduce_combine for
     argmin/argmax, which RCCL has no operator for).
 """
 import numpy as np
 
 from .. import backend, codegen, comm, runtime
-from ..array import distarray, extent as ext
+from ..array import combine, distarray, extent as ext
+from ..array.combine import COMBINE_CALLS  # noqa: F401  (read by tests as engine.COMBINE_CALLS)
 from ..array.distarray import DistArrayImpl, LocalWrapper, ReplicatedArray
-from ..util import prod
 from .broadcast import Broadcast
 from .local import CodegenError, LowerEnv, Pre, UntraceableMapper, has_location, host_evaluate, lower
 
@@ -383,148 +383,10 @@ def run_reduce(children, child_to_var, local_op, axis, dtype, accumulate_fn, til
         geom = {'offset': ext.ravelled_pos(ex.ul, in_shape_full) if nd else 0}
       else:
         geom = {'decompose': True, 'tshape': ex.shape, 'tul': ex.ul, 'ashape': in_shape_full}
-    partials[ex] = (dst, be.reduce(root, opname, inputs, ex.shape if nd else (), ax,
-                                   dst.shape if dst.ndim else (), out_dtype, geom))
+    partials[ex] = be.reduce(root, opname, inputs, ex.shape if nd else (), ax,
+                             dst.shape if dst.ndim else (), out_dtype, geom)
   output = distarray.create(out_shape, out_dtype, reducer=accumulate_fn, tile_hint=tile_hint)
-  combine_partials(output, partials, tiles, ax, opname,
-                   value_dtype=codegen.acc_dtype(opname, root.dtype) if arg else None)
+  # the same list on every rank, from the global tile map
+  combine.land(output, [(ext.index_for_reduction(ex, ax), w, partials.get(ex)) for ex, w in tiles.items()], opname,
+               value_dtype=codegen.acc_dtype(opname, root.dtype) if arg else None)
   return output
-
-
-def _identity(op, dt):
-  dt = np.dtype(dt)
-  if op == 'sum':
-    return 0.0
-  if dt.kind == 'f':
-    return float('inf') if op == 'min' else float('-inf')
-  if dt.kind == 'b':
-    return 1.0 if op == 'min' else 0.0
-  info = np.iinfo(dt)
-  return float(info.max) if op == 'min' else float(info.min)
-
-
-# How many times each cross-rank combine ran (tests assert the branch taken).
-COMBINE_CALLS = {'reduce_scatter': 0, 'all_reduce': 0, 'gather_combine': 0, 'arg_gather': 0}
-
-
-def combine_partials(output, partials, tiles, ax, opname, value_dtype=None):
-  """Merge tile partials into ``output`` (reference: _reduce_mapper ->
-  output.update(dst, partial) -> tile.merge with accumulate_fn).
-
-  ``value_dtype``: for argmin/argmax, the dtype of the partial values (the
-  same on every rank, also on ranks without a local partial)."""
-  import torch
-  ctx = runtime.get()
-  be = backend.get()
-  arg = opname in ('argmin', 'argmax')
-  # every rank computes the same alignment decision from the global tile map
-  dsts = [(ext.index_for_reduction(ex, ax), w) for ex, w in tiles.items()]
-  seen = set()
-  aligned = True
-  for d, w in dsts:
-    if d not in output.tiles or (d.ul, d.lr) in seen or \
-        (w != -1 and ctx.owner(output.tiles[d]) != ctx.owner(w)):
-      aligned = False
-      break
-    seen.add((d.ul, d.lr))
-  if aligned:
-    for ex, (d, part) in partials.items():
-      t = output.local.get(d)
-      if t is None:
-        continue
-      data = part[1] if arg else part
-      if data.dtype != t.data.dtype:
-        conv = torch.empty(t.data.shape, dtype=t.data.dtype, device=t.data.device)
-        be.copy_region(conv, (0,) * conv.dim(), data, (0,) * conv.dim(), tuple(conv.shape))
-        data = conv
-      t.data = data.reshape(t.data.shape)
-      t.written = [d]
-    return
-  shape = output.shape
-  if arg:
-    # values keep their own dtype end to end: int64 compares as int64 (a
-    # float64 detour would merge distinct values above 2^53)
-    vdt = backend.torch_dtype(value_dtype) if value_dtype is not None else None
-    for _, (d, (pv, pi)) in partials.items():
-      vdt = pv.dtype
-    if vdt is None:
-      raise ValueError('combine_partials: value dtype of the arg-reduction unknown on this rank')
-    full_v = torch.zeros(shape, dtype=vdt, device=ctx.device)
-    full_i = torch.empty(shape, dtype=torch.int64, device=ctx.device)
-    be.fill(full_i, backend.FILL_CONST, 9.3e18, 0.0, 0, (0,) * len(shape), shape)
-    for ex, (d, (pv, pi)) in partials.items():
-      _arg_merge_region(be, full_v, full_i, d, pv, pi, opname)
-    if ctx.distributed:
-      COMBINE_CALLS['arg_gather'] += 1
-      vs = comm.all_gather_stack(full_v.reshape(-1))
-      is_ = comm.all_gather_stack(full_i.reshape(-1))
-      _, best_i = be.argcombine(opname, vs, is_)
-      full_i = best_i.reshape(shape)
-    for d, t in output.local.items():
-      _copy_out(be, t, full_i, d)
-    return
-  full = torch.empty(shape, dtype=backend.torch_dtype(output.dtype), device=ctx.device)
-  be.fill(full, backend.FILL_CONST, _identity(opname, output.dtype), 0.0, 0, (0,) * len(shape), shape)
-  for ex, (d, part) in partials.items():
-    be.merge(full, None, d.ul, part.reshape(d.shape if d.ndim else ()), opname, fastpath=False)
-  if ctx.distributed:
-    if opname != 'sum':
-      # min / max across ranks: gather every rank's partial and fold them in
-      # rank order with the local kernels' NaN rule (np.minimum / np.maximum
-      # propagate NaN; the collective library's MIN / MAX need not)
-      COMBINE_CALLS['gather_combine'] += 1
-      stack = comm.all_gather_stack(full.reshape(-1))
-      n = full.numel()
-      folded = torch.empty((n,), dtype=full.dtype, device=full.device)
-      be.finalize(opname, stack.reshape(-1), ctx.world_size, n, folded)
-      full = folded.reshape(shape)
-    elif _rank_slabs(output, ctx):
-      COMBINE_CALLS['reduce_scatter'] += 1
-      (d, t), = output.local.items()
-      comm.reduce_scatter_rows(t.data, full, opname)
-      t.written = [d]
-      return
-    else:
-      COMBINE_CALLS['all_reduce'] += 1
-      comm.all_reduce(full, opname)
-  for d, t in output.local.items():
-    _copy_out(be, t, full, d)
-
-
-def _rank_slabs(output, ctx):
-  """True iff output tiles are world_size equal row slabs, tile k on rank k."""
-  if len(output.shape) == 0 or len(output.tiles) != ctx.world_size:
-    return False
-  exs = sorted(output.tiles.items(), key=lambda kv: kv[0].ul)
-  n = exs[0][0].shape[0]
-  for k, (ex, w) in enumerate(exs):
-    if ctx.owner(w) != k or ex.ul[0] != k * n or ex.lr[0] - ex.ul[0] != n:
-      return False
-    if any(ex.ul[d] != 0 or ex.lr[d] != output.shape[d] for d in range(1, len(output.shape))):
-      return False
-  return True
-
-
-def _copy_out(be, tile, full, d):
-  if d.ndim == 0:
-    be.copy_region(tile.data, (), full, (), ())
-  else:
-    be.copy_region(tile.data, (0,) * d.ndim, full, d.ul, d.shape)
-  tile.written = [d]
-
-
-def _arg_merge_region(be, full_v, full_i, d, pv, pi, opname):
-  import torch
-  shape = d.shape if d.ndim else ()
-  n = prod(shape)
-  old_v = torch.empty(shape, dtype=full_v.dtype, device=full_v.device)
-  old_i = torch.empty(shape, dtype=torch.int64, device=full_v.device)
-  ul = d.ul if d.ndim else ()
-  be.copy_region(old_v, (0,) * len(shape), full_v, ul, shape)
-  be.copy_region(old_i, (0,) * len(shape), full_i, ul, shape)
-  pvc = pv.reshape(shape).to(full_v.dtype) if pv.dtype != full_v.dtype else pv.reshape(shape)
-  vs = torch.stack([old_v.reshape(n), pvc.reshape(n)])
-  is_ = torch.stack([old_i.reshape(n), pi.reshape(n)])
-  bv, bi = be.argcombine(opname, vs, is_)
-  be.copy_region(full_v, ul, bv.reshape(shape), (0,) * len(shape), shape)
-  be.copy_region(full_i, ul, bi.reshape(shape), (0,) * len(shape), shape)

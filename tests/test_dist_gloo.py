@@ -109,7 +109,18 @@ def _body(rank, world, port, W, q):
     xf = expr.arange((40, 30)).force()
     nxf = np.arange(1200.).reshape(40, 30)
     yf = expr.arange((30, 20)).force()
+    dot_mod = sys.modules['spartan_amd.expr.dot']
+    n_ar, n_rs, n_ov = E.COMBINE_CALLS['all_reduce'], E.COMBINE_CALLS['reduce_scatter'], dot_mod.OVERLAPPED_CALLS
     np.testing.assert_array_equal(expr.dot(xf, yf).glom(), nxf @ np.arange(600.).reshape(30, 20))
+    # the K-split partials are summed by ONE all-reduce (counted since the route
+    # lives in array/combine.py) -- except with one row slab per rank (W == world,
+    # 40 rows), where the overlapped path reduces slab by slab and counts itself
+    overlapped = dot_mod.OVERLAPPED_CALLS - n_ov
+    assert overlapped == (1 if W == world else 0)
+    assert E.COMBINE_CALLS['all_reduce'] == n_ar + 1 - overlapped
+    assert E.COMBINE_CALLS['reduce_scatter'] == n_rs
+    lab = np.arange(40) % 7
+    np.testing.assert_array_equal(expr.bincount(expr.from_numpy(lab)).glom(), np.bincount(lab))
     np.testing.assert_array_equal(expr.map(xf, np.sqrt).glom(), np.sqrt(nxf))
     np.testing.assert_allclose(expr.sum(expr.sqrt(xf), 0).glom(), O.sum_tiles(np.sqrt(nxf), 0, W),
                                rtol=1e-12)
@@ -135,7 +146,6 @@ def _body(rank, world, port, W, q):
     # dot: K-split with the A column-strip exchange and the partial reduction
     a = rng.rand((24, 36), 1, np.float64)
     b = rng.rand((36, 20), 2, np.float64)
-    dot_mod = sys.modules['spartan_amd.expr.dot']
     n0 = dot_mod.OVERLAPPED_CALLS
     got = expr.dot(expr.from_numpy(a), expr.from_numpy(b)).glom()
     np.testing.assert_allclose(got, a @ b, rtol=1e-12)

@@ -12,7 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import spartan_amd  # noqa: E402
 from spartan_amd import backend, expr  # noqa: E402
-from spartan_amd.array import blocks, distarray, extent as ext, transfer  # noqa: E402
+from spartan_amd.array import blocks, combine, distarray, extent as ext, transfer  # noqa: E402
 from spartan_amd.expr import base as ebase, join as ejoin  # noqa: E402
 from spartan_amd.examples import kmeans as km  # noqa: E402
 
@@ -48,7 +48,7 @@ def main():
                            (km, '_count_join', '_count_join'), (blocks, 'scatter_updates', 'scatter_updates'),
                            (transfer, 'download', 'download'), (transfer, 'upload', 'upload'),
                            (km, '_step_domain', '_step_domain'), (km, '_fused_step', '_fused_step'),
-                           (km, '_deliver_full', '_deliver_full'), (torch, 'empty', 'torch.empty')):
+                           (combine, 'deliver', 'combine.deliver'), (torch, 'empty', 'torch.empty')):
     wrap(obj, name, label)
   # the registered join functions were bound at import: re-register the wrapped ones
   ejoin.register_join(km.kmeans_count_mapper, km._count_join)

@@ -11,7 +11,7 @@ import numpy as np  # noqa: E402
 import spartan_amd  # noqa: E402
 from spartan_amd import backend, expr  # noqa: E402
 from spartan_amd.expr import engine, plan_cache  # noqa: E402
-from spartan_amd.array import distarray, transfer  # noqa: E402
+from spartan_amd.array import combine, distarray, transfer  # noqa: E402
 
 spartan_amd.initialize()
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
@@ -32,8 +32,9 @@ def wrap(mod, name, label=None):
 
 
 be = backend.get()
-for nm in ['bind', 'fetch_inputs', 'combine_partials', 'driving_tiles', 'materialise_pres']:
+for nm in ['bind', 'fetch_inputs', 'driving_tiles', 'materialise_pres']:
   wrap(engine, nm)
+wrap(combine, 'land', 'combine.land')
 wrap(plan_cache, 'signature')
 wrap(plan_cache, '_instantiate')
 wrap(distarray, 'create', 'distarray.create')
