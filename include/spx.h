@@ -109,6 +109,16 @@ int spx_reduce_finalize(int op, int acc_dtype, int out_dtype, const void* part_v
                         const int64_t* part_idx, int64_t P, int64_t n, void* out,
                         void* out_val, void* stream);
 
+/* The two partial sets of a paired column + row sum (a generated 'cols'
+ * kernel that also writes per-tile row sums) in one launch; dtype SPX_F32 or
+ * SPX_F64 for partials and results alike.  col_part[P][n] -> col_out[n]
+ * exactly as spx_reduce_finalize(SPX_OP_SUM, dtype, dtype, ...) folds it
+ * (bit-identical).  row_part[CT][R] -> row_out[R], folded in ct order in an
+ * fp64 accumulator and rounded once to dtype.
+ */
+int spx_reduce_finalize_pair(int dtype, const void* col_part, int64_t P, int64_t n, void* col_out,
+                             const void* row_part, int64_t CT, int64_t R, void* row_out, void* stream);
+
 /* ------------------------------------------------------------------ merge
  * dst[region] = reducer(dst[region], src) with the reference's mask rule:
  * elements whose mask byte is 0 are replaced (first write), others reduced;

@@ -18,6 +18,7 @@ import os
 import subprocess
 import tempfile
 import threading
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -146,6 +147,21 @@ ROWDOT_INTERLEAVE = True
 # 2.8-3.1 at one block (tools/cfg2_il.py, profiles/r05_cfg2_interleave.txt)
 COLS_BLOCKS_PER_CU = 2
 COLS_INTERLEAVE = False
+# paired sums (HipBackend.reduce): an axis-0 sum that an axis-1 sum of the
+# same tree over the same tensors has followed before also writes per-tile
+# row sums, and the following axis-1 sum is served from them without a second
+# pass over the inputs (cfg2: one 12.9 GB read per step instead of two).
+# PAIR_SUMS: the master switch; PAIR_MIN_BYTES: launches reading less than
+# this are never paired (a second pass is cheap, the bookkeeping is not)
+PAIR_SUMS = True
+PAIR_MIN_BYTES = 64 << 20
+PAIR_SEEN_MAX = 256  # pair keys remembered (seen-then-speculate)
+PAIR_MEMO_MAX = 16   # row-sum tensors held for a following axis-1 sum
+# libspx entry points that take tables of device pointers (addresses the
+# pointer scan of _call cannot see): calling one drops every held row sum.
+# The binding has one, and HipBackend does not call it today (comm.py does,
+# on exchange buffers of its own)
+PAIR_TABLE_CALLS = frozenset(['spx_sendrecv'])
 
 
 def _num_cus():
@@ -272,6 +288,72 @@ def plan_reduce(root, op, ins, res16, view, out_dtype, idx_geom, ncu):
   return ReducePlan(kind, classes, V, U, rowinv, klpr, kfull, kint, nblk, P, n_out, arg, direct, pdt, args)
 
 
+def pair_eligible(root, op, ins, view, plan):
+  """Whether the launch ``plan`` (plan_reduce's, for ``view``) may run as the
+  paired kernel (codegen.gen_reduce pair=True): a floating column sum of one
+  (R, I) matrix without row dot or interleaving, on the vector path, whose
+  column tiles cover I exactly, that reads at least PAIR_MIN_BYTES.  Pure
+  integer arithmetic, no device; reads PAIR_SUMS and PAIR_MIN_BYTES."""
+  O, R, I, vstr = view
+  if not PAIR_SUMS or plan.kind != 'cols' or op != 'sum' or O != 1 or plan.kint or not plan.args.flags & 1:
+    return False
+  if not codegen.is_float(codegen.acc_dtype(op, root.dtype)) or codegen.rowdots(root):
+    return False
+  lpr, CT = 1 << plan.args.aux[2], plan.args.aux[3]
+  if I != CT * lpr * plan.V:
+    return False
+  read = sum(np.dtype(dt).itemsize * (R if st[1] else 1) * (I if st[2] else 1) for (_, dt), st in zip(ins, vstr))
+  return read >= PAIR_MIN_BYTES
+
+
+def _scalar_values(root):
+  """The values of a tree's Sc leaves, in walk order."""
+  return tuple((n.slot, n.value) for n in codegen.walk(root) if isinstance(n, codegen.Sc))
+
+
+def _mem_range(t):
+  """[first byte, one past the last) of the allocation behind tensor ``t``:
+  what any view of the same storage can reach."""
+  st = t.untyped_storage()
+  return st.data_ptr(), st.data_ptr() + st.nbytes()
+
+
+class _ClearHooked(dict):
+  """A dict whose clear() also calls ``on_clear`` (HipBackend._reduce_plans and
+  eval_cache's store: clearing either drops the paired-sum state)."""
+  on_clear = None
+
+  def clear(self):
+    dict.clear(self)
+    if self.on_clear is not None:
+      self.on_clear()
+
+
+_pair_backends = weakref.WeakSet()  # backends whose held row sums an eval_cache.clear() drops
+
+
+def _drop_all_pair_memos():
+  for be in list(_pair_backends):
+    be._pair_memo.clear()
+
+
+def _watch_eval_cache(be):
+  """From now on eval_cache.clear() drops ``be``'s held row sums."""
+  from .expr.base import eval_cache
+  if not isinstance(eval_cache.cache, _ClearHooked):
+    eval_cache.cache = _ClearHooked(eval_cache.cache)
+    eval_cache.cache.on_clear = _drop_all_pair_memos
+  _pair_backends.add(be)
+
+
+# One held row-sum result: the tensor, weak references to the operand tensors
+# it was computed from, their _version counters and allocations, the tree's
+# scalar values.
+_PairEntry = namedtuple('_PairEntry', 'rows refs versions ranges scalars')
+# The previous reduce call when it was an eligible axis-0 sum.
+_PairLast = namedtuple('_PairLast', 'key refs scalars')
+
+
 class HipBackend:
   """Launches libspx.so / generated kernels on the current HIP stream."""
   name = 'hip'
@@ -285,7 +367,15 @@ class HipBackend:
     self.kernel_events = None  # optional list of (name, start, end) HIP events (bench)
     self._names = {}
     self._sig_fns = {}
-    self._reduce_plans = {}  # backend.reduce launch plans (see reduce)
+    self._reduce_plans = _ClearHooked()  # backend.reduce launch plans (see reduce)
+    self._reduce_plans.on_clear = self._pair_reset
+    # paired sums (see reduce): the pair keys seen, the previous call when it
+    # was an eligible axis-0 sum, the held row sums by pair key, and whether
+    # the call under way is the paired launch itself
+    self._pair_seen = set()
+    self._pair_last = None
+    self._pair_memo = {}
+    self._pair_own = False
 
   # ---------------------------------------------------------------- utils
   def stream(self):
@@ -321,6 +411,11 @@ class HipBackend:
     """One ahead-of-time libspx call ``name`` on the current stream, which
     every compute entry point takes last.  ``timed``: between _events(), logged
     under ``name``.  The arguments go to ctypes as they are."""
+    if self._pair_memo and not self._pair_own:
+      if name in PAIR_TABLE_CALLS:
+        self._pair_memo.clear()
+      else:
+        self._pair_scan([a.value for a in args if isinstance(a, ctypes.c_void_p) and a.value])
     ev = self._events() if timed else None
     if ev is not None:
       self.kernel_events.append((name, ev[0], ev[1]))
@@ -360,6 +455,8 @@ class HipBackend:
     if self.launch_log is not None:
       self.launch_log.append(grid)
     args.grid = grid
+    if self._pair_memo and not self._pair_own:
+      self._pair_scan([p for p in list(args.ptr) + [args.out0, args.out1] if p])
     ev = self._events()
     _check(self.lib.spx_launch(fn, grid, 1, 1, 256, 0, ctypes.byref(args), ctypes.sizeof(args),
                                current_stream()), 'spx_launch')
@@ -446,13 +543,25 @@ class HipBackend:
     # (the pointer's residue mod 16, not just 16-byte alignment: the vector
     # width of narrow types needs only 8 or 4 bytes, so two pointers with the
     # same 16-alignment verdict can still differ in what V they allow)
-    pkey = (root.sig(), op, tuple((s, inputs[s].dtype, tuple(inputs[s].shape), inputs[s].stride(),
-                                   inputs[s].data_ptr() % 16) for s in slots),
-            tuple(in_shape), axis, tuple(out_shape), np.dtype(out_dtype).str,
+    ikey = tuple((s, inputs[s].dtype, tuple(inputs[s].shape), inputs[s].stride(), inputs[s].data_ptr() % 16)
+                 for s in slots)
+    pkey = (root.sig(), op, ikey, tuple(in_shape), axis, tuple(out_shape), np.dtype(out_dtype).str,
             None if idx_geom is None else repr(sorted(idx_geom.items())),
             # the module's grid / layout knobs shape the plan too
             (ROWS_GRID_PER_CU, COLS_BLOCKS_PER_CU, COLS_INTERLEAVE, ROWDOT_BLOCKS_PER_CU, ROWDOT_UNROLL,
-             ROWDOT_INTERLEAVE))
+             ROWDOT_INTERLEAVE, PAIR_SUMS, PAIR_MIN_BYTES))
+    # paired sums.  A pair key names a tree over operand layouts (not
+    # values).  An eligible axis-0 sum (pair_eligible) followed at once by
+    # the axis-1 sum of the same tree over the same tensor objects and scalar
+    # values puts the key into _pair_seen; from then on the axis-0 sum of that
+    # key runs the paired kernel and holds the row sums (_run_pair), and the
+    # axis-1 sum that follows takes them (_pair_take) if nothing has touched
+    # the operands since
+    last, self._pair_last = self._pair_last, None
+    if op == 'sum' and axis == 1 and len(in_shape) == 2 and last is not None:
+      got = self._pair_take(last, (root.sig(), ikey, tuple(in_shape)), root, inputs, slots, out_shape, out_dtype)
+      if got is not None:
+        return got
     entry = self._reduce_plans.get(pkey)
     if entry is None:
       ins = [(s, np_dtype(inputs[s].dtype)) for s in slots]
@@ -492,17 +601,110 @@ class HipBackend:
         if fn is None:
           src, kname = codegen.named(codegen.gen_reduce(root, ins, *sig[3:]), 'spx_reduce', plan.kind)
           fn = self._sig_fns[sig] = self.kernel(src, kname)
+      pk = None
+      if (axis == 0 and len(in_shape) == 2 and np.dtype(out_dtype) == plan.pdt and
+          pair_eligible(root, op, ins, view, plan)):
+        pk = (root.sig(), ikey, tuple(in_shape))
       if len(self._reduce_plans) >= 512:
         self._reduce_plans.clear()
-      entry = self._reduce_plans[pkey] = (plan, fn, out_device(inputs, slots))
+      entry = self._reduce_plans[pkey] = (plan, fn, out_device(inputs, slots), pk)
+    pk = entry[3]
+    if pk is not None:
+      self._pair_memo.pop(pk, None)  # a new axis-0 sum of the key: what an earlier one left is not taken any more
+      self._pair_last = _PairLast(pk, tuple(weakref.ref(inputs[s]) for s in slots), _scalar_values(root))
+      if pk in self._pair_seen:
+        return self._run_pair(entry, root, inputs, slots, out_shape, out_dtype)
     return self._run_reduce(entry, root, op, inputs, slots, out_shape, out_dtype)
+
+  def _pair_reset(self):
+    self._pair_seen.clear()
+    self._pair_memo.clear()
+    self._pair_last = None
+
+  def _pair_scan(self, ptrs):
+    """Drop every held row sum one of whose operand allocations holds one of
+    the device addresses ``ptrs`` (the pointer arguments of a call about to be
+    made; reads count too).  libspx and the generated kernels write through
+    raw pointers, which no tensor's _version sees."""
+    for key, e in list(self._pair_memo.items()):
+      if any(lo <= p < hi for p in ptrs for lo, hi in e.ranges):
+        self._pair_memo.pop(key, None)
+
+  def _pair_take(self, last, key, root, inputs, slots, out_shape, out_dtype):
+    """An axis-1 sum with pair key ``key`` right after the eligible axis-0 sum
+    ``last``.  When the two are one tree over the same tensor objects and
+    scalar values the key is noted as seen, and the row sums that the axis-0
+    call left (if it ran paired) are returned if they are still those of these
+    operands -- handed over once: the entry goes.  Else None."""
+    scalars = _scalar_values(root)
+    if not (last.key == key and last.scalars == scalars and len(last.refs) == len(slots) and
+            all(r() is inputs[s] for r, s in zip(last.refs, slots))):
+      return None
+    if len(self._pair_seen) >= PAIR_SEEN_MAX:
+      self._pair_seen.clear()
+    self._pair_seen.add(key)
+    e = self._pair_memo.get(key)
+    if e is None:
+      return None
+    if not (e.scalars == scalars and len(e.refs) == len(slots) and
+            all(r() is inputs[s] and inputs[s]._version == v for r, v, s in zip(e.refs, e.versions, slots)) and
+            tuple(e.rows.shape) == tuple(out_shape) and e.rows.dtype == torch_dtype(out_dtype)):
+      return None
+    del self._pair_memo[key]
+    return e.rows
+
+  def _pair_hold(self, key, rows, root, inputs, slots):
+    """Hold ``rows`` for the axis-1 sum that follows the paired launch."""
+    memo = self._pair_memo
+    while len(memo) >= PAIR_MEMO_MAX:
+      del memo[next(iter(memo))]
+    drop = lambda _r, memo=memo, key=key: memo.pop(key, None)  # an operand died
+    ts = [inputs[s] for s in slots]
+    memo[key] = _PairEntry(rows, tuple(weakref.ref(t, drop) for t in ts), tuple(t._version for t in ts),
+                           tuple(_mem_range(t) for t in ts), _scalar_values(root))
+    _watch_eval_cache(self)
+
+  def _run_pair(self, entry, root, inputs, slots, out_shape, out_dtype):
+    """The paired launch of a planned axis-0 sum: the plan's grid and argument
+    block, the paired kernel, both partial sets through
+    spx_reduce_finalize_pair; returns the column sums and holds the row
+    sums."""
+    import torch
+    p, _, dev, key = entry
+    R, CT, lpr = p.args.dim[1], p.args.aux[3], 1 << p.args.aux[2]
+    ins = tuple((s, np_dtype(inputs[s].dtype)) for s in slots)
+    sig = ('reduce_pair', root.sig(), ins, p.classes, p.V, p.U, p.rowinv, lpr)
+    fn = self._sig_fns.get(sig)
+    if fn is None:
+      src, kname = codegen.named(codegen.gen_reduce(root, list(ins), p.classes, 'cols', 'sum', p.V, p.U, p.rowinv, lpr,
+                                                    True, False, pair=True), 'spx_reduce', 'pair')
+      fn = self._sig_fns[sig] = self.kernel(src, kname)
+    tdt = torch_dtype(p.pdt)
+    cols = torch.empty(tuple(out_shape), dtype=tdt, device=dev)
+    rows = torch.empty((R,), dtype=tdt, device=dev)
+    part_c = torch.empty((p.P * p.n_out,), dtype=tdt, device=dev)
+    part_r = torch.empty((CT * R,), dtype=tdt, device=dev)
+    args = codegen.KArgs.from_buffer_copy(p.args)
+    _scalars_into(root, args)
+    for s in slots:
+      args.ptr[s] = inputs[s].data_ptr()
+    args.out0, args.out1 = part_c.data_ptr(), part_r.data_ptr()
+    self._pair_own = True  # these two calls read the operands of held row sums: no scan
+    try:
+      self.launch(fn, p.nblk, args)
+      self._call('spx_reduce_finalize_pair', spx_dtype(p.pdt), _ptr(part_c), p.P, p.n_out, _ptr(cols), _ptr(part_r),
+                 CT, R, _ptr(rows), timed=False)
+    finally:
+      self._pair_own = False
+    self._pair_hold(key, rows, root, inputs, slots)
+    return cols
 
   def _run_reduce(self, entry, root, op, inputs, slots, out_shape, out_dtype):
     """Launch a planned reduction (first call and replay alike): the plan's
     kernel, grid and argument block with this call's scalars, pointers and
     output buffers, then the finalize pass over the P partials."""
     import torch
-    p, fn, dev = entry
+    p, fn, dev = entry[:3]
     tpdt = torch_dtype(p.pdt)  # (arg ops: the values' dtype, pdt == the accumulator's)
     out_shape = tuple(out_shape)
     if p.arg:

@@ -80,6 +80,7 @@ def _signatures():
       'spx_launch': ([VP, U32, U32, U32, U32, U32, VP, SZ, VP], I),
       'spx_fill': ([I, I, VP, I, _I64P, _I64P, _I64P, F64, F64, U64, VP], I),
       'spx_reduce_finalize': ([I, I, I, VP, VP, I64, I64, VP, VP, VP], I),
+      'spx_reduce_finalize_pair': ([I, VP, I64, I64, VP, VP, I64, I64, VP, VP], I),
       'spx_merge': ([I, I, VP, VP, I, _I64P, _I64P, _I64P, VP, I, I, VP], I),
       'spx_copy_region': ([I, VP, _I64P, _I64P, I, VP, _I64P, _I64P, I, _I64P, VP], I),
       'spx_gemm': ([I, I64, I64, I64, VP, I64, VP, I64, VP, I64, F64, F64, VP], I),

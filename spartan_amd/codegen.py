@@ -715,17 +715,20 @@ class _Red:
     self.act = ctype(self.adt)
     self.arg = op in ('argmin', 'argmax')
 
-  def preamble(self, kind):
+  def preamble(self, kind, pair=False):
     fn, ocml = _expr_fn(self.root, self.inputs)
     L = [PRELUDE, _ocml_decls(ocml), fn, _comb_fns(self.op, self.adt)]
-    if self.rds or kind == 'rows':
+    if self.rds or kind == 'rows' or pair:
       L += [SHFL, ROW_ALLSUM]
     return L + [GFLAT] if self.arg else L
 
+  def value(self, j, sfx=''):
+    """The tree's value of the loaded element j (names suffixed sfx), in the accumulator's type."""
+    return '(%s)%s' % (self.act, _call_expr(self.inputs, j, n_rd=len(self.rds), sfx=sfx))
+
   def update(self, j, idx_expr, sfx=''):
     """Accumulator j takes the tree's value of the loaded element j (names suffixed sfx)."""
-    val = '(%s)%s' % (self.act, _call_expr(self.inputs, j, n_rd=len(self.rds), sfx=sfx))
-    return _acc_update(self.op, j, val, idx_expr)
+    return _acc_update(self.op, j, self.value(j, sfx), idx_expr)
 
   def loads(self, V, base_expr, vdim):
     b = []
@@ -773,7 +776,8 @@ class _Red:
             [ind + '  ' + x for x in body(1)] + [ind + '}'])
 
 
-def gen_reduce(root, inputs, classes, kind, op, vec, unroll=None, rowinv=(), lpr=None, full=False, interleave=False):
+def gen_reduce(root, inputs, classes, kind, op, vec, unroll=None, rowinv=(), lpr=None, full=False, interleave=False,
+               pair=False):
   """Fused map+reduce.  kind 'rows' (reduce over contiguous R of (O, R), one
   or more blocks per segment), 'rowsp' (the same for short R: several
   segments per wave, LPR lanes each, butterfly combine) or 'cols' (reduce over
@@ -788,16 +792,30 @@ def gen_reduce(root, inputs, classes, kind, op, vec, unroll=None, rowinv=(), lpr
   then compiles to 4 straight DPP adds: with a run-time LPR every row paid
   6 uniform branches, and the column masks a select per element -- cfg5's
   loop body was 641 instructions per 8 rows, issue-bound beside the loads.
+
+  'cols' only: ``pair`` makes the kernel also write, for every row r of its
+  column tile ct, the sum of the tree's values over the tile's columns to
+  out1[ct * R + r] (the [p][n] layout of the finalize pass, p = ct, n = R):
+  a following sum over the other axis is then a fold of CT partials per row
+  instead of a second pass over the inputs.  Floating sums only, without row
+  dot or interleaving, ``lpr`` and ``full`` compiled in and the vector path
+  only (the kernel has no scalar path: the launch must have flags & 1 set,
+  I == CT * lpr * vec and O == 1).  The column side is the unpaired kernel's,
+  addition for addition.
   """
   assert op in REDOPS and kind in ('rows', 'rowsp', 'cols')
   c = _Red(root, inputs, classes, op, vec)
   if c.rds and kind != 'cols':
     raise NotImplementedError('a fused row dot needs the column-reduce skeleton')
+  if pair and not (kind == 'cols' and op == 'sum' and is_float(c.adt) and not c.rds and not interleave and
+                   lpr and full and vec > 1):
+    raise NotImplementedError('paired row sums need a floating column sum without row dot or interleaving, '
+                              'on the vector path with lpr and full compiled in')
   if kind == 'cols':
-    kernel = _reduce_cols(c, unroll, rowinv, lpr, full, interleave)
+    kernel = _reduce_cols(c, unroll, rowinv, lpr, full, interleave, pair)
   else:
     kernel = (_reduce_rows if kind == 'rows' else _reduce_rowsp)(c)
-  return '\n'.join(c.preamble(kind) + kernel)
+  return '\n'.join(c.preamble(kind, pair) + kernel)
 
 
 def _reduce_rows(c):
@@ -911,7 +929,7 @@ def _reduce_rowsp(c):
 
 # 'cols': blocks over (column tile, O, row chunk) of (O, R, I), lanes along I.
 # _Cols: what gen_reduce was given for it and what follows from that.
-_Cols = collections.namedtuple('_Cols', 'U rowinv lpr full interleave lv pact kahan bcast')
+_Cols = collections.namedtuple('_Cols', 'U rowinv lpr full interleave lv pact kahan bcast pair')
 
 
 def _cols_load_srcs(s, dt, cls, V, off):
@@ -932,7 +950,7 @@ def _cols_load_srcs(s, dt, cls, V, off):
   return ['%s[off]' % p], pre
 
 
-def _cols_one_row(c, k, V, rv, sfx, masked, bcu=None):
+def _cols_one_row(c, k, V, rv, sfx, masked, bcu=None, ps=None):
   """Loads + (row dots) + accumulator updates of row ``rv`` into names
   suffixed ``sfx``; split in (load lines, compute lines) so an unrolled
   body issues every row's loads before the first use.  ``bcu``: this
@@ -969,6 +987,19 @@ def _cols_one_row(c, k, V, rv, sfx, masked, bcu=None):
     for j in range(V):
       cp.append('%s = %s + (%s)x%d_%d%s * (%s)x%d_%d%s;' % (n, n, ct, rd.a.slot, j, sfx, ct, rd.w.slot, j, sfx))
     cp.append('%s = row_allsum(%s, LPR);' % (n, n))
+  if ps is not None:
+    # paired row sums: each value is computed once, goes into its column
+    # accumulator as in the unpaired kernel and into the lane's row sum (the
+    # V values folded in index order), which waits in slot ``ps`` for the
+    # flush that follows the next loads
+    for j in range(V):
+      cp.append('const %s pv%d%s = %s;' % (c.act, j, sfx, c.value(j, sfx)))
+      cp.append(_acc_update(c.op, j, 'pv%d%s' % (j, sfx), '(%s)' % rv))
+    fold = 'pv0%s' % sfx
+    for j in range(1, V):
+      fold = '(%s + pv%d%s)' % (fold, j, sfx)
+    cp.append('prs%d = %s; prr%d = %s;' % (ps, fold, ps, rv))
+    return ld, cp
   upd = [c.update(j, '(%s)' % rv, sfx) for j in range(V)]
   if masked:
     cp += ['if (colok) {'] + ['  ' + x for x in upd] + ['}']
@@ -983,7 +1014,7 @@ def _cols_body(c, k, V):
   masked = bool(c.rds)
   # row-dot kernels: every lane of a row group takes part in the DPP row
   # sum, so lanes past the last column read column 0 and use zeros
-  b = ['{' if masked else 'if (col < I) {']
+  b = ['{' if masked or k.pair else 'if (col < I) {']  # (pair: full, every lane holds a column)
   b.append('  const bool colok = %s; (void)colok;' % ('true' if (k.full and k.lpr and V == c.vec) else 'col < I'))
   b.append('  const i64 cc = colok ? col : 0; (void)cc;')
   for (s, dt), cls in zip(c.inputs, c.classes):
@@ -1017,6 +1048,26 @@ def _cols_body(c, k, V):
     b.append('  for (i64 sb = p * (%d * STEP); sb < R; sb += P * (%d * STEP)) {' % (U, U))
     b.append('  const i64 r0 = sb; i64 r1 = sb + %d * STEP; if (r1 > R) r1 = R;' % U)
   b.append('  i64 r = r0 + w * RPW + sub;')
+  # paired row sums, in two deferred stages so that neither the cross-lane
+  # steps nor the store's acknowledgement sits between one row's use and the
+  # next row's loads.  A row's lane sum waits in prs (its row in prr, -1:
+  # none); after the NEXT iteration's loads are issued it is summed over the
+  # row group (``red``: under the load latency) into pst / prq; that value is
+  # stored at the top of the iteration after that, BEFORE its loads
+  # (``sto``): the wait for the loads then has no younger store to wait for
+  # (the empty asm pins the group sum where it stands: left alone, the
+  # compiler sinks it behind the row's arithmetic, where the cross-lane
+  # latency is exposed; a sched_barrier there as well measured the same.
+  # row_allsum with a compile-time LPR: DPP inside 16 lanes, ds_bpermute
+  # across them -- on the GPU as fast as reading the four 16-lane sums
+  # through v_readlane, and the same butterfly as the row kernels' own lane
+  # combine)
+  red = lambda u: ('pst%d = row_allsum(prs%d, LPR); asm volatile("" : "+v"(pst%d)); prq%d = prr%d;'
+                   % (u, u, u, u, u))
+  sto = lambda u: ('if (cl == 0 && prq%d >= 0) ((GLOBAL %s*)a.out1)[ct * R + prq%d] = pst%d;' % (u, act, u, u))
+  if k.pair:
+    b.append('  %s %s; i64 %s;' % (act, ', '.join('prs%d = 0, pst%d = 0' % (u, u) for u in range(U)),
+                                   ', '.join('prr%d = -1, prq%d = -1' % (u, u) for u in range(U))))
   if U > 1:
     b.append('  for (; r + %d * STEP < r1; r += %d * STEP) {' % (U - 1, U))
     lds, cps = [], []
@@ -1028,15 +1079,22 @@ def _cols_body(c, k, V):
                % (s_, ct, s_, s_, s_))
     for u in range(U):
       b.append('    const i64 r_%d = r + %d * STEP;' % (u, u))
-      ld, cp = _cols_one_row(c, k, V, 'r_%d' % u, '_u%d' % u, masked, u if k.bcast else None)
+      ld, cp = _cols_one_row(c, k, V, 'r_%d' % u, '_u%d' % u, masked, u if k.bcast else None,
+                             u if k.pair else None)
       lds += ld
       cps += cp
+    if k.pair:
+      lds = [sto(u) for u in range(U)] + lds + [red(u) for u in range(U)]
     b += ['    ' + x for x in lds + cps]
     b.append('  }')
   b.append('  for (; r < r1; r += STEP) {')
-  ld, cp = _cols_one_row(c, k, V, 'r', '', masked)
+  ld, cp = _cols_one_row(c, k, V, 'r', '', masked, None, 0 if k.pair else None)
+  if k.pair:
+    ld = [sto(0)] + ld + [red(0)]
   b += ['    ' + x for x in ld + cp]
   b.append('  }')
+  if k.pair:
+    b += ['  ' + f(u) for f in (sto, red, sto) for u in range(U)]  # drain both stages
   if k.interleave:
     if k.lv:
       for j in range(V):
@@ -1061,7 +1119,7 @@ def _cols_body(c, k, V):
   return b
 
 
-def _reduce_cols(c, unroll, rowinv, lpr, full, interleave):
+def _reduce_cols(c, unroll, rowinv, lpr, full, interleave, pair=False):
   """'cols': the block's 4 * RPW row groups stride over its chunk of R, LDS combine."""
   act, arg, vec = c.act, c.arg, c.vec
   U = unroll or cols_unroll(c.inputs, c.classes, vec)
@@ -1075,7 +1133,7 @@ def _reduce_cols(c, unroll, rowinv, lpr, full, interleave):
   if c.rds and lpr == 16 and U > 1 and U <= 16:
     bcast = tuple(s for (s, dt), cls in zip(c.inputs, c.classes)
                   if cls == 'b' and s not in rowinv and np.dtype(dt).itemsize in (4, 8))
-  k = _Cols(U, rowinv, lpr, full, interleave, lv, pact, lv and pact == 'double' and act == 'double', bcast)
+  k = _Cols(U, rowinv, lpr, full, interleave, lv, pact, lv and pact == 'double' and act == 'double', bcast, pair)
   L = ['KERN void spx_reduce(KArgs a) {']
   L.append('  const i64 O = a.dim[0], R = a.dim[1], I = a.dim[2];')
   if lpr:
@@ -1089,11 +1147,14 @@ def _reduce_cols(c, unroll, rowinv, lpr, full, interleave):
   L.append('  const i64 o = rest % O, p = rest / O;')
   L.append('  const u32 t = tid(); const i64 lane = t & 63, w = t >> 6;')
   L.append('  const i64 sub = lane >> lpr_log, cl = lane & (LPR - 1);')
-  L.append('  const i64 V = (a.flags & 1) ? %d : 1;' % vec)
+  L.append('  constexpr i64 V = %d;' % vec if pair else '  const i64 V = (a.flags & 1) ? %d : 1;' % vec)
   L.append('  const i64 col = ct * (LPR * V) + cl * V;')
   L.append('  const i64 r0 = p * chunk; i64 r1 = r0 + chunk; if (r1 > R) r1 = R;')
   L += c.acc_decls('  ', pact if lv else None)
-  L += c.both_paths('  ', lambda V: _cols_body(c, k, V)) + c.to_global('  ')
+  if pair:  # the vector path alone
+    L += ['  ' + x for x in _cols_body(c, k, vec)]
+  else:
+    L += c.both_paths('  ', lambda V: _cols_body(c, k, V)) + c.to_global('  ')
   # LDS combine over the 4*RPW row groups sharing a column, in row-group
   # order (in the partials' type: fp64 for an interleaved fp32 sum)
   L.append('  SHARED %s sv[256 * %d];' % (pact, vec))

@@ -296,11 +296,13 @@ __device__ __forceinline__ void arg_fold(int op, V v, i64 vi, V& b, i64& bi) {
   if (vi != ARG_EMPTY && (bi == ARG_EMPTY || better)) { b = v; bi = vi; }
 }
 
-__global__ __launch_bounds__(256) void k_finalize(int op, int acc_dt, int out_dt, const void* pv,
-                                                  const i64* pi, i64 P, i64 n, void* out,
-                                                  void* out_val) {
-  i64 stride = (i64)gridDim.x * 256;
-  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+// Block ``blk`` of ``nblk`` 256-thread blocks: one thread per output, the P
+// partials folded in p order (k_finalize, and the column half of
+// k_finalize_pair).
+__device__ __forceinline__ void finalize_thin(int op, int acc_dt, int out_dt, const void* pv, const i64* pi, i64 P,
+                                              i64 n, void* out, void* out_val, i64 blk, i64 nblk) {
+  i64 stride = nblk * 256;
+  for (i64 i = blk * 256 + threadIdx.x; i < n; i += stride) {
     if ((op == SPX_OP_ARGMIN || op == SPX_OP_ARGMAX) && is_float_dt(acc_dt)) {
       double b = ld_f(pv, acc_dt, i);
       i64 bi = pi[i];
@@ -335,20 +337,27 @@ __global__ __launch_bounds__(256) void k_finalize(int op, int acc_dt, int out_dt
   }
 }
 
+__global__ __launch_bounds__(256) void k_finalize(int op, int acc_dt, int out_dt, const void* pv,
+                                                  const i64* pi, i64 P, i64 n, void* out,
+                                                  void* out_val) {
+  finalize_thin(op, acc_dt, out_dt, pv, pi, P, n, out, out_val, blockIdx.x, gridDim.x);
+}
+
 // Many partials per output (a tall column reduce splits R over P ~ 2048
 // blocks, e.g. cfg5's (1e8, 64) gradient): one block per output, threads
 // stride over P in order, then a fixed-shape LDS tree -- deterministic run to
 // run.  Float partials are combined in fp64.
-__global__ __launch_bounds__(256) void k_finalize_wide(int op, int acc_dt, int out_dt, const void* pv,
-                                                       const i64* pi, i64 P, i64 n, void* out,
-                                                       void* out_val) {
+// (finalize_wide: block ``blk`` of ``nblk``; k_finalize_wide, and the column
+// half of k_finalize_pair)
+__device__ __forceinline__ void finalize_wide(int op, int acc_dt, int out_dt, const void* pv, const i64* pi, i64 P,
+                                              i64 n, void* out, void* out_val, i64 blk, i64 nblk) {
   __shared__ double sv[256];
   __shared__ i64 si[256];
   __shared__ i64 sw[256];  // integer arg values (compared as int64)
   const int t = threadIdx.x;
   const bool arg = op == SPX_OP_ARGMIN || op == SPX_OP_ARGMAX;
   const bool fl = is_float_dt(acc_dt);
-  for (i64 i = blockIdx.x; i < n; i += gridDim.x) {
+  for (i64 i = blk; i < n; i += nblk) {
     double b = 0.0;
     i64 bw = 0;
     i64 bi = ARG_EMPTY;
@@ -414,6 +423,55 @@ __global__ __launch_bounds__(256) void k_finalize_wide(int op, int acc_dt, int o
   }
 }
 
+__global__ __launch_bounds__(256) void k_finalize_wide(int op, int acc_dt, int out_dt, const void* pv,
+                                                       const i64* pi, i64 P, i64 n, void* out,
+                                                       void* out_val) {
+  finalize_wide(op, acc_dt, out_dt, pv, pi, P, n, out, out_val, blockIdx.x, gridDim.x);
+}
+
+// Whether spx_reduce_finalize folds [P][n] partials with k_finalize_wide, and
+// the grid of either kernel.
+static bool finalize_is_wide(i64 P, i64 n) { return P >= 32 && n <= 16384; }
+static unsigned finalize_grid(i64 P, i64 n) {
+  return finalize_is_wide(P, n) ? (unsigned)(n < 4096 ? n : 4096) : (unsigned)grid_for(n);
+}
+
+// The two partial sets of a paired column + row sum (codegen.gen_reduce
+// pair=True) in one launch.  Blocks [0, gc): the column partials [P][n],
+// exactly as spx_reduce_finalize folds them (same kernel body, same grid, so
+// bit-identical).  Blocks [gc, gc + gr): the row partials [CT][R], one thread
+// per row, folded in ct order in an fp64 accumulator and rounded once to the
+// value type (fp64 values: folded in fp64).
+__global__ __launch_bounds__(256) void k_finalize_pair(int dt, const void* cpv, i64 P, i64 n, void* cout, int wide,
+                                                       unsigned gc, const void* rpv, i64 CT, i64 R, void* rout) {
+  if (blockIdx.x < gc) {
+    if (wide) finalize_wide(SPX_OP_SUM, dt, dt, cpv, nullptr, P, n, cout, nullptr, blockIdx.x, gc);
+    else finalize_thin(SPX_OP_SUM, dt, dt, cpv, nullptr, P, n, cout, nullptr, blockIdx.x, gc);
+    return;
+  }
+  const i64 stride = (i64)(gridDim.x - gc) * 256;
+  for (i64 r = (i64)(blockIdx.x - gc) * 256 + threadIdx.x; r < R; r += stride) {
+    double acc = ld_f(rpv, dt, r);
+    for (i64 ct = 1; ct < CT; ++ct) acc += ld_f(rpv, dt, ct * R + r);
+    st_f(rout, dt, r, acc);
+  }
+}
+
+extern "C" int spx_reduce_finalize_pair(int dtype, const void* col_part, int64_t P, int64_t n, void* col_out,
+                                        const void* row_part, int64_t CT, int64_t R, void* row_out, void* stream) {
+  if (dtype != SPX_F32 && dtype != SPX_F64)
+    return set_err(SPX_EINVAL, "spx_reduce_finalize_pair: dtype must be float32 or float64");
+  if (P < 1 || n < 0 || CT < 1 || R < 0) return set_err(SPX_EINVAL, "spx_reduce_finalize_pair: bad P/n/CT/R");
+  if (n == 0 && R == 0) return SPX_OK;
+  if ((n > 0 && (!col_part || !col_out)) || (R > 0 && (!row_part || !row_out)))
+    return set_err(SPX_EINVAL, "spx_reduce_finalize_pair: null pointer");
+  const unsigned gc = n > 0 ? finalize_grid(P, n) : 0, gr = R > 0 ? (unsigned)grid_for(R) : 0;
+  k_finalize_pair<<<gc + gr, 256, 0, S(stream)>>>(dtype, col_part, P, n, col_out, finalize_is_wide(P, n) ? 1 : 0, gc,
+                                                  row_part, CT, R, row_out);
+  LAUNCH_CHECK("spx_reduce_finalize_pair");
+  return SPX_OK;
+}
+
 extern "C" int spx_reduce_finalize(int op, int acc_dtype, int out_dtype, const void* part_val,
                                    const int64_t* part_idx, int64_t P, int64_t n, void* out,
                                    void* out_val, void* stream) {
@@ -424,12 +482,12 @@ extern "C" int spx_reduce_finalize(int op, int acc_dtype, int out_dtype, const v
   if (n == 0) return SPX_OK;
   if ((op == SPX_OP_ARGMIN || op == SPX_OP_ARGMAX) && !part_idx)
     return set_err(SPX_EINVAL, "spx_reduce_finalize: arg op needs part_idx");
-  if (P >= 32 && n <= 16384)
-    k_finalize_wide<<<(unsigned)(n < 4096 ? n : 4096), 256, 0, S(stream)>>>(op, acc_dtype, out_dtype, part_val,
-                                                                            part_idx, P, n, out, out_val);
+  if (finalize_is_wide(P, n))
+    k_finalize_wide<<<finalize_grid(P, n), 256, 0, S(stream)>>>(op, acc_dtype, out_dtype, part_val, part_idx, P, n,
+                                                                out, out_val);
   else
-    k_finalize<<<grid_for(n), 256, 0, S(stream)>>>(op, acc_dtype, out_dtype, part_val, part_idx, P, n,
-                                                   out, out_val);
+    k_finalize<<<finalize_grid(P, n), 256, 0, S(stream)>>>(op, acc_dtype, out_dtype, part_val, part_idx, P, n, out,
+                                                           out_val);
   LAUNCH_CHECK("spx_reduce_finalize");
   return SPX_OK;
 }
