@@ -35,7 +35,8 @@ extern "C" {
  * spx_topk_workspace, spx_topk, spx_topk_plan, spx_knn_workspace, spx_knn, spx_knn_plan,
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
- * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan */
+ * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
+ * spx_als_plan, spx_als_solve */
 
 /* error codes */
 #define SPX_OK 0
@@ -662,6 +663,49 @@ int spx_csrmm(int dtype, int64_t m, int64_t n, int64_t p, int64_t nnz, const int
               int64_t g, void* workspace, size_t workspace_bytes, int prepared, void* stream);
 int spx_csr_todense(int dtype, int64_t m, int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* col,
                     const void* val, void* D, int64_t ldd, void* stream);
+
+/* ------------------------------- sparse transpose helper, ALS row solves
+ * spx_csr_rowids: out[k] = r0 + i for every k in [rowptr[i], rowptr[i + 1])
+ * -- the global row number of every stored entry of a row slab that starts at
+ * row r0, which the transpose sorts along with the values.
+ * rowptr is m + 1 int64 with rowptr[m] == nnz, out is nnz int32; every word of
+ * out is written once by a plain vector store.  SPX_EINVAL for a negative size
+ * or a null pointer, SPX_ENOTSUP for r0 + m above the int32 range; m == 0 or
+ * nnz == 0 is SPX_OK with no launch.
+ *
+ * spx_als_solve: the per-row solve of alternating least squares, replacing the
+ * per-row numpy lstsq loop of the reference (spartan/examples/als.py).  A is
+ * m x n in CSR as for spx_csrmm, Y is dense row-major n x f with leading
+ * dimension ldy, X is m x f with leading dimension ldx.  For every row i, with
+ * K_i the stored entries of the row whose value is not zero,
+ *
+ *   G_i = sum_{k in K_i} y_{col[k]} y_{col[k]}^T + lambda |K_i| I,
+ *   b_i = sum_{k in K_i} val[k] y_{col[k]},      X[i, :] = G_i^{-1} b_i
+ *
+ * by Cholesky and two substitutions.  A row with K_i empty gets zeros.  A row
+ * whose factorization meets a pivot that is not positive and finite gets NaN
+ * in all f entries, and *info -- a device word the call clears first --
+ * counts those rows.  Everything is computed in float64 for both dtypes; the
+ * dtype says what is loaded and stored.  One wave owns a row and walks its
+ * entries in stored order, so there are no float atomics, a call is bitwise
+ * reproducible, and a row's bits depend only on its own entries, Y, f, lambda
+ * and dtype -- never on m or on the rows around it.  The columns must lie in
+ * [0, n): the kernel does not check them.  X may not alias Y.
+ *
+ * spx_als_plan (pure host): fmax (64) and the rows one 256-thread workgroup
+ * solves for this f (0 where f is outside 1 .. fmax).
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a dtype code
+ * out of range, a negative size, f < 1, ldy or ldx below f, a lambda that is
+ * negative or not finite, a null pointer where it is read (col / val / Y only
+ * with nnz > 0) or X == Y; SPX_ENOTSUP for a dtype other than float32 /
+ * float64 or f > fmax.  m == 0 is SPX_OK with no launch.  Additive since
+ * ABI 3. */
+int spx_csr_rowids(int64_t m, int64_t nnz, const int64_t* rowptr, int64_t r0, int32_t* out, void* stream);
+int spx_als_plan(int dtype, int64_t f, int64_t* fmax, int64_t* rows_per_block);
+int spx_als_solve(int dtype, int64_t m, int64_t n, int64_t f, int64_t nnz, const int64_t* rowptr, const int32_t* col,
+                  const void* val, const void* Y, int64_t ldy, double lambda, void* X, int64_t ldx, int32_t* info,
+                  void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

@@ -159,6 +159,10 @@ class SparseDistArray(distarray.DistArray):
     out.has_sorted_indices = True
     return out
 
+  def transposed(self, tile_hint=None):
+    """Collective: the transpose as a new SparseDistArray (``transposed``)."""
+    return transposed(self, tile_hint)
+
 
 # ---------------------------------------------------------------- builders
 def slab_extents(shape, tile_hint=None):
@@ -262,3 +266,133 @@ def empty(shape, dtype=np.float32, tile_hint=None):
     return np.zeros(r1 - r0 + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, dtype)
 
   return from_csr_pieces(shape, np.dtype(dtype), tile_hint, piece, lambda r0, r1: 0)
+
+
+# --------------------------------------------------------------- transpose
+def _through(be, src, perm):
+  """``src[perm]`` for 1-d device tensors (``take``)."""
+  import torch
+  out = torch.empty_like(src)
+  n = int(src.numel())
+  be.take(src, perm, out, (1, n, 1), 0, n)
+  return out
+
+
+def _sorted_by_column(be, t, r0):
+  """(col, row, val) of the tile ``t`` whose first row is ``r0``, ordered by
+  (column, row): the entries are stored in row order and the sort is stable."""
+  import torch
+  nz = t.nnz
+  rows = torch.empty((nz,), dtype=torch.int32, device=t.col.device)
+  be.csr_rowids(t.rowptr, r0, rows)
+  keys = torch.empty_like(t.col)
+  perm = torch.empty((nz,), dtype=torch.int64, device=t.col.device)
+  be.sort(t.col, keys, perm, (1, nz, 1))
+  return keys, _through(be, rows, perm), _through(be, t.val, perm)
+
+
+def _cuts(be, col, n, bounds):
+  """Host int64 array: how many of the column numbers ``col`` lie below each
+  of the ascending ``bounds`` (1 .. n) -- ``bincount``, an inclusive ``scan`` and
+  a ``take`` of the counts at the bounds."""
+  import torch
+  per = torch.empty((n,), dtype=torch.int64, device=col.device)
+  be.bincount(be.contiguous(col, np.int64), per)
+  cum = torch.empty_like(per)
+  be.scan(per, cum, (1, n, 1))
+  at = _up(np.asarray(bounds, np.int64) - 1, np.int64)
+  ends = torch.empty((len(bounds),), dtype=torch.int64, device=col.device)
+  be.take(cum, at, ends, (1, n, 1), 0, n)
+  return transfer.download(ends).reshape(-1).astype(np.int64)
+
+
+def transposed(S, tile_hint=None):
+  """Collective: ``S.T`` as a SparseDistArray of shape (n, m) in the row slabs
+  of ``slab_extents((n, m), tile_hint)``.  Every row of the
+  result has ascending columns, explicit zeros are kept, and neither the
+  layout of ``S`` nor the worker count changes a bit of it.
+
+  Each local slab orders its entries by (column, row) with the stable radix
+  sort, cuts them at the row bounds of the target slabs and sends every piece
+  to the target's owner: one ``gather_regions`` for each of the three arrays
+  (old column, old row, value).  A target concatenates its pieces in source
+  order -- row order -- and, when there is more than one source slab, sorts
+  them once more, stably, by the old column.  The per-piece counts reach every
+  rank in one all-reduce; they lay out the exchange and give ``slab_nnz``."""
+  import torch
+  from .. import codegen
+  ctx = runtime.get()
+  be = backend.get()
+  m, n = S.shape
+  if m > 2 ** 31 - 1:
+    raise NotImplementedError('%d rows are outside the int32 column range of the transpose' % m)
+  tiles = slab_extents((n, m), tile_hint)
+  src = S.slabs()
+  dst = sorted(tiles.items(), key=lambda kv: kv[0].ul[0])
+  bounds = [e.lr[0] for e, _ in dst]
+
+  # 1. every local slab in (column, row) order, and its cuts at the target bounds
+  ordered = {}
+  cnt = np.zeros((len(src), len(dst)), np.int64)
+  for si, (e, _) in enumerate(src):
+    if e in S.local and S.local[e].nnz:
+      t = S.local[e]
+      ordered[si] = _sorted_by_column(be, t, e.ul[0])
+      cnt[si] = np.diff(np.concatenate([[0], _cuts(be, t.col, n, bounds)]))
+  if ctx.distributed:
+    dev = _up(cnt.reshape(-1), np.int64)
+    comm.all_reduce(dev, 'sum')
+    cnt = transfer.download(dev).reshape(cnt.shape).astype(np.int64)
+  totals = cnt.sum(axis=0)
+  total = int(totals.sum())
+  slab_nnz = {e: int(c) for (e, _), c in zip(dst, totals)}
+
+  # 2. one exchange per array: the pieces laid out by (target, source)
+  got = [{}, {}, {}]
+  if total:
+    base = np.concatenate([[0], np.cumsum(totals)])
+    requests = [(ext.create((int(base[j]),), (int(base[j + 1]),), (total,)), ctx.owner(w))
+                for j, (_, w) in enumerate(dst) if totals[j]]
+    asked = [j for j in range(len(dst)) if totals[j]]
+    for which, dtype in ((0, np.int32), (1, np.int32), (2, S.dtype)):
+      xt, xl = {}, {}
+      for j in asked:
+        at = int(base[j])
+        for si, (_, w) in enumerate(src):
+          c = int(cnt[si, j])
+          if c:
+            x = ext.create((at,), (at + c,), (total,))
+            xt[x] = w
+            if si in ordered:
+              a = int(cnt[si, :j].sum())
+              xl[x] = ordered[si][which][a:a + c]
+            at += c
+      arr = distarray.from_tiles((total,), dtype, xt, xl)
+      res = distarray.gather_regions(arr, requests)
+      got[which] = {asked[qi]: t for qi, t in res.items()}
+
+  # 3. every local target slab: rows in order, columns ascending, a tile-local rowptr
+  local = {}
+  for j, (e, w) in enumerate(dst):
+    if not ctx.is_local(w):
+      continue
+    rows = e.lr[0] - e.ul[0]
+    if not totals[j]:
+      local[e] = SparseTile(e, torch.zeros((rows + 1,), dtype=torch.int64, device=ctx.device),
+                            _up(np.zeros(0), np.int32), _up(np.zeros(0), S.dtype))
+      continue
+    keys, col, val = (be.contiguous(got[which][j]).reshape(-1) for which in range(3))
+    nz = int(keys.numel())
+    if len(src) > 1:  # pieces of several slabs: row order within a piece, not across the pieces of one column
+      perm = torch.empty((nz,), dtype=torch.int64, device=keys.device)
+      be.sort(keys, None, perm, (1, nz, 1))
+      col, val = _through(be, col, perm), _through(be, val, perm)
+    rel = torch.empty((nz,), dtype=torch.int64, device=keys.device)
+    be.map(codegen.Cast(codegen.Op('subtract', [codegen.In(0, np.int32), codegen.Sc(0, int(e.ul[0]))]), np.int64),
+           {0: keys}, rel)
+    per = torch.zeros((rows + 1,), dtype=torch.int64, device=keys.device)
+    be.bincount(rel, per[:rows])
+    rowptr = torch.empty_like(per)
+    be.scan(per, rowptr, (1, rows + 1, 1), exclusive=True)
+    local[e] = SparseTile(e, rowptr, col, val)
+  return SparseDistArray((n, m), S.dtype, tiles, local, slab_nnz)

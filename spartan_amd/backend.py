@@ -29,7 +29,7 @@ from .layout import broadcast_strides, coalesce, reduce_view, contiguous_strides
 from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP_CODE, FILL_CONST, FILL_ARANGE,
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
-                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, gemm_plan,
+                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, als_plan, gemm_plan,
                      GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
@@ -1352,6 +1352,48 @@ class HipBackend:
     if m == 0 or n == 0:
       return
     self._call('spx_csr_todense', spx_dtype(dt), m, int(n), nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(D), ldd)
+
+  def csr_rowids(self, rowptr, r0, out):
+    """``out`` (nnz,) int32 = ``r0`` + the tile-local row of every stored entry
+    of the CSR row pointers ``rowptr`` (spx_csr_rowids).  Asynchronous."""
+    import torch
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.numel() < 1 or not rowptr.is_contiguous():
+      raise ValueError('csr_rowids: rowptr must be a contiguous int64 vector of m + 1 entries')
+    if out.dim() != 1 or out.dtype != torch.int32 or not out.is_contiguous():
+      raise ValueError('csr_rowids: out must be a contiguous int32 vector')
+    m, nnz = int(rowptr.numel()) - 1, int(out.numel())
+    if int(r0) < 0 or int(r0) + m > 2 ** 31 - 1:
+      raise ValueError('csr_rowids: rows %d .. %d are outside the int32 range' % (r0, int(r0) + m))
+    if m == 0 or nnz == 0:
+      return
+    self._call('spx_csr_rowids', m, nnz, _ptr(rowptr), int(r0), _ptr(out))
+
+  def als_solve(self, rowptr, col, val, n, Y, lam, X):
+    """``X`` (m, f) = the ALS row solves of A (m, n) in CSR against the factor
+    ``Y`` (n, f) with regularisation ``lam`` (spx_als_solve): row i solves
+    (sum y y^T + lam |K_i| I) x = sum a y over the entries of the row whose
+    value is not zero.  ``Y`` and ``X`` may be padded (unit column stride).
+    Returns the one-element int32 device tensor ``info`` (the rows whose
+    factorization failed, which hold NaN); nothing here reads it.  The columns
+    must lie in [0, n).  Asynchronous on the current stream."""
+    import torch
+    m, nnz, dt = self._csr('als_solve', rowptr, col, val, n)
+    _, f, ldy = self._matrix('als_solve: Y', Y, int(n), None, dt)
+    _, _, ldx = self._matrix('als_solve: X', X, m, f, dt)
+    fmax = als_plan(dt, 0)[0]
+    if f < 1 or f > fmax:
+      raise ValueError('als_solve: f = %d is outside [1, fmax = %d]' % (f, fmax))
+    lam = float(lam)
+    if not (lam >= 0.0 and np.isfinite(lam)):
+      raise ValueError('als_solve: lam = %r is not finite and non-negative' % lam)
+    if X.data_ptr() == Y.data_ptr() and Y.numel() and X.numel():
+      raise ValueError('als_solve: X may not be Y')
+    info = torch.zeros((1,), dtype=torch.int32, device=X.device)
+    if m == 0:
+      return info
+    self._call('spx_als_solve', spx_dtype(dt), m, int(n), f, nnz, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(Y), ldy,
+               lam, _ptr(X), ldx, _ptr(info))
+    return info
 
   @staticmethod
   def _kmeans_counters_offset(D):

@@ -130,6 +130,9 @@ def _signatures():
       'spx_csrmm_workspace': ([I, I64, I64, I64], I64),
       'spx_csrmm': ([I, I64, I64, I64, I64, VP, VP, VP, VP, I64, VP, I64, F64, F64, I64, VP, SZ, I, VP], I),
       'spx_csr_todense': ([I, I64, I64, I64, VP, VP, VP, VP, I64, VP], I),
+      'spx_csr_rowids': ([I64, I64, VP, I64, VP, VP], I),
+      'spx_als_plan': ([I, I64, _I64P, _I64P], I),
+      'spx_als_solve': ([I, I64, I64, I64, I64, VP, VP, VP, VP, I64, F64, VP, I64, VP, VP], I),
       'spx_comm_load': ([CP], I),
       'spx_comm_unique_id': ([VP, I64], I),
       'spx_comm_init': ([VP, I64, I, I, VPP], I),
@@ -376,6 +379,13 @@ def csrmm_plan(dtype, m, nnz, p):
   one row, the row length above which a row is cut into chunks of T for whole
   workgroups, and the rows one workgroup covers."""
   return _float_plan('csrmm', 'sparse', dtype, 3, (m, nnz, p), 'negative size (%d, %d, %d)')
+
+
+def als_plan(dtype, f):
+  """(fmax, rows_per_block) of spx_als_solve for ``f`` features of ``dtype``,
+  from the library: the largest f the kernel holds in a wave's registers and
+  the rows one workgroup solves (0 where f is outside 1 .. fmax)."""
+  return _float_plan('als', 'ALS', dtype, 2, (f,), 'negative f = %d')
 
 
 def __getattr__(name):

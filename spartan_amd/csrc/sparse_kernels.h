@@ -1,5 +1,6 @@
-// sparse_kernels.h -- CSR x dense (spx_csrmm) and CSR -> dense (spx_csr_todense)
-// for gfx950.  Included from spx.hip.
+// sparse_kernels.h -- CSR x dense (spx_csrmm), CSR -> dense (spx_csr_todense) and
+// the row number of every stored entry (spx_csr_rowids) for gfx950 (DESIGN.md
+// 3.20, 3.22).  Included from spx.hip.
 //
 // C = alpha A B + beta C with A (m x n) in CSR (rowptr int64, col int32, val T)
 // and B, C dense row-major.  The kernel is bound by the bytes of val / col and
@@ -255,6 +256,23 @@ static hipError_t todense_run(i64 m, i64 n, const i64* rowptr, const int32_t* co
   return hipGetLastError();
 }
 
+// -------------------------------------------------------------- row ids
+// out[k] = r0 + i for every k in [rowptr[i], rowptr[i + 1]): the row number of
+// every stored entry (the transpose's new column).  A wave per
+// row, plain vector stores; an entry belongs to one row, so every word is
+// written once.
+__global__ __launch_bounds__(BLOCK) void csr_rowids(i64 m, i64 nnz, const i64* __restrict__ rowptr, i64 r0,
+                                                    int32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const i64 waves = (i64)gridDim.x * (BLOCK / 64);
+  for (i64 r = (i64)blockIdx.x * (BLOCK / 64) + threadIdx.x / 64; r < m; r += waves) {
+    i64 s = rowptr[r], e = rowptr[r + 1];
+    if (s < 0) s = 0;  // a malformed rowptr: never outside out
+    if (e > nnz) e = nnz;
+    for (i64 k = s + lane; k < e; k += 64) out[k] = (int32_t)(r0 + r);
+  }
+}
+
 }  // namespace spx_sp
 
 // ------------------------------------------------------------------ C ABI
@@ -333,5 +351,22 @@ extern "C" int spx_csr_todense(int dtype, int64_t m, int64_t n, int64_t nnz, con
                                   : spx_sp::todense_run<double>(m, n, rowptr, col, (const double*)val, (double*)D,
                                                                 ldd, S(stream));
   if (e != hipSuccess) return set_err(SPX_EHIP, "spx_csr_todense failed: %s", hipGetErrorString(e));
+  return SPX_OK;
+}
+
+extern "C" int spx_csr_rowids(int64_t m, int64_t nnz, const int64_t* rowptr, int64_t r0, int32_t* out, void* stream) {
+  if (m < 0 || nnz < 0 || r0 < 0)
+    return set_err(SPX_EINVAL, "spx_csr_rowids: negative size (m %lld, nnz %lld, r0 %lld)", (long long)m,
+                   (long long)nnz, (long long)r0);
+  if (m > SP_MAX || nnz > SP_MAX || r0 > SP_MAX || r0 + m > 0x7fffffffLL)
+    return set_err(SPX_ENOTSUP, "spx_csr_rowids: rows %lld .. %lld are above the int32 range", (long long)r0,
+                   (long long)(r0 + m));
+  if (m == 0 || nnz == 0) return SPX_OK;
+  if (!rowptr || !out) return set_err(SPX_EINVAL, "spx_csr_rowids: null rowptr / out");
+  const i64 blocks = (m + spx_sp::BLOCK / 64 - 1) / (spx_sp::BLOCK / 64);
+  hipLaunchKernelGGL(spx_sp::csr_rowids, dim3((int)std::min<i64>(blocks, spx_sp::MAX_GRID)), dim3(spx_sp::BLOCK), 0,
+                     S(stream), m, nnz, rowptr, r0, out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(SPX_EHIP, "spx_csr_rowids failed: %s", hipGetErrorString(e));
   return SPX_OK;
 }

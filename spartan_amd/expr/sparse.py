@@ -16,8 +16,10 @@ be done with one:
     plan and given to every slab, so a row's bits do not depend on the layout;
   * ``todense(S)``: ``csr_todense`` per slab, same slabs;
   * ``sum(S, axis=1 | None)``: ``dot`` with a ones vector, then the dense
-    reduce; ``axis=0`` needs the transpose (a follow-up);
-  * ``S * c``, ``c * S``: the same structure with scaled values.
+    reduce; ``axis=0`` refuses: it is ``sum(sparse_transpose(S), axis=1)``;
+  * ``S * c``, ``c * S``: the same structure with scaled values;
+  * ``sparse_transpose(S)``: the transpose under its own name,
+    ``SparseDistArray.transposed``.
 
 Everything else refuses a sparse operand with a ``TypeError`` that names
 ``todense()`` -- at construction where the operand is visibly sparse, and in
@@ -146,6 +148,22 @@ class SparseScaleExpr(SparseExpr):
     return S.with_values(scaled)
 
 
+class SparseTransposeExpr(SparseExpr):
+  _members = ('array',)
+
+  def compute_shape(self):
+    return tuple(self.array.shape[::-1])
+
+  def compute_dtype(self):
+    return np.dtype(self.array.dtype)
+
+  def pretty_str(self):
+    return 'SparseTranspose[%d](%s)' % (self.expr_id, self.array)
+
+  def _evaluate(self, deps):
+    return sparray.transposed(deps['array'], self.tile_hint)
+
+
 class ToDenseExpr(Expr):
   _members = ('array',)
   accepts_sparse = True
@@ -249,6 +267,37 @@ def sparse_dot(S, x):
   return distarray.from_tiles(out_shape, dt, tiles, local)
 
 
+def sparse_als_solve(S, y, lam):
+  """One ALS half-step on arrays: (X, infos) with X[i] the solution of row i of
+  the SparseDistArray ``S`` (m, n) against the dense factor ``y`` (n, f) --
+  ``als_solve`` on every local slab with ``y`` brought whole to every rank, as
+  ``sparse_dot`` brings its right operand.  X is dense, (m, f), of S's dtype, in
+  row slabs aligned with S's on the same workers; ``infos`` are the slabs'
+  one-element device counters of failed rows, unread.  Collective: one gather
+  of y; no cross-rank reduction."""
+  import torch
+  if getattr(y, 'sparse', False):
+    raise TypeError('als: the factor is dense: ' + TODENSE)
+  ctx = runtime.get()
+  be = backend.get()
+  m, n = S.shape
+  if len(y.shape) != 2 or y.shape[0] != n:
+    raise ValueError('als: a factor of %d rows is needed, got shape %s' % (n, tuple(y.shape)))
+  f = int(y.shape[1])
+  dt = np.dtype(S.dtype)
+  Y = be.contiguous(whole(y), dt).reshape(n, f)
+  tiles, local, infos = {}, {}, []
+  for e, w in S.tiles.items():
+    d = _out_extent(e, (m, f))
+    tiles[d] = w
+    if e in S.local:
+      t = S.local[e]
+      X = torch.empty((e.shape[0], f), dtype=backend.torch_dtype(dt), device=ctx.device)
+      infos.append(be.als_solve(t.rowptr, t.col, t.val, n, Y, lam, X))
+      local[d] = X
+  return distarray.from_tiles((m, f), dt, tiles, local), infos
+
+
 def todense_array(S):
   import torch
   if not getattr(S, 'sparse', False):
@@ -266,6 +315,26 @@ def todense_array(S):
 def todense(S):
   """The dense array of a sparse one, in the same row slabs."""
   return ToDenseExpr(array=as_sparse_expr(S))
+
+
+def sparse_transpose(S, tile_hint=None):
+  """The transpose of a sparse array as a sparse expression of shape (n, m), in
+  the row slabs of ``tile_hint`` (default: the rows dealt evenly to the
+  workers).  ``glom()`` of it is scipy's ``A.T.tocsr()`` with sorted indices,
+  bit for bit; explicit zeros are kept.  This is the one way to the transpose:
+  ``S.T``, ``transpose(S)``, ``dot(dense, S)`` and ``sum(S, axis=0)`` still refuse.
+  Column sums are ``sum(sparse_transpose(S), axis=1)``, and ``X @ S`` is
+  ``transpose(dot(sparse_transpose(S), transpose(X)))``."""
+  S = as_sparse_expr(S)
+  if tile_hint is not None:
+    tile_hint = tuple(int(h) for h in tile_hint)
+    if len(tile_hint) != 2:
+      raise ValueError('tile_hint %s does not match the 2-d shape %s' % (tile_hint, tuple(S.shape[::-1])))
+    if tile_hint[1] < S.shape[0]:
+      raise NotImplementedError('tile_hint %s cuts axis 1: sparse arrays are tiled in row slabs, every tile '
+                                'spanning all %d columns (column-cut tilings are out of scope)'
+                                % (tile_hint, S.shape[0]))
+  return SparseTransposeExpr(array=S, tile_hint=tile_hint)
 
 
 def sparse_sum(S, axis=None):
