@@ -439,9 +439,46 @@ static unsigned finalize_grid(i64 P, i64 n) {
 // The two partial sets of a paired column + row sum (codegen.gen_reduce
 // pair=True) in one launch.  Blocks [0, gc): the column partials [P][n],
 // exactly as spx_reduce_finalize folds them (same kernel body, same grid, so
-// bit-identical).  Blocks [gc, gc + gr): the row partials [CT][R], one thread
-// per row, folded in ct order in an fp64 accumulator and rounded once to the
-// value type (fp64 values: folded in fp64).
+// bit-identical).  Blocks [gc, gc + gr): the row partials [CT][R], each row
+// folded in ct order in an fp64 accumulator and rounded once to the value
+// type (fp64 values: folded in fp64).  A block takes PAIR_ROWS consecutive
+// rows: all 256 threads load the [ct][rows] tile into LDS in passes of
+// PAIR_CTS ct (every load of a pass issued before the first LDS write: 16
+// independent loads per thread, each ct a contiguous PAIR_ROWS-value
+// segment), then one thread per row folds its column of the tile, the
+// accumulator carried across the passes.  (One thread per row walking its CT
+// partials alone kept 512 waves on 128 dependent-latency loads each: 0.041 ms
+// for cfg2's 17 MB.)
+constexpr int PAIR_ROWS = 32, PAIR_CTS = 128;
+
+template <typename T>
+__device__ __forceinline__ void finalize_pair_rows(T* tile, const T* rp, i64 CT, i64 R, T* rout, i64 blk) {
+  constexpr int LANES = 256 / PAIR_ROWS, LOADS = PAIR_CTS / LANES;
+  const int t = threadIdx.x, j = t % PAIR_ROWS, c = t / PAIR_ROWS;
+  const i64 r = blk * PAIR_ROWS + j;
+  const bool ok = r < R;
+  double acc = 0.0;
+  for (i64 c0 = 0; c0 < CT; c0 += PAIR_CTS) {
+    const int nct = CT - c0 < PAIR_CTS ? (int)(CT - c0) : PAIR_CTS;
+    T v[LOADS];
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int ct = c + LANES * i;
+      v[i] = (ok && ct < nct) ? rp[(c0 + ct) * R + r] : (T)0;
+    }
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) tile[(c + LANES * i) * PAIR_ROWS + j] = v[i];
+    __syncthreads();
+    if (t < PAIR_ROWS) {
+      int ct = 0;
+      if (c0 == 0) { acc = (double)tile[t]; ct = 1; }
+      for (; ct < nct; ++ct) acc += (double)tile[ct * PAIR_ROWS + t];
+    }
+    __syncthreads();  // the next pass rewrites the tile
+  }
+  if (t < PAIR_ROWS && ok) rout[r] = (T)acc;
+}
+
 __global__ __launch_bounds__(256) void k_finalize_pair(int dt, const void* cpv, i64 P, i64 n, void* cout, int wide,
                                                        unsigned gc, const void* rpv, i64 CT, i64 R, void* rout) {
   if (blockIdx.x < gc) {
@@ -449,12 +486,10 @@ __global__ __launch_bounds__(256) void k_finalize_pair(int dt, const void* cpv, 
     else finalize_thin(SPX_OP_SUM, dt, dt, cpv, nullptr, P, n, cout, nullptr, blockIdx.x, gc);
     return;
   }
-  const i64 stride = (i64)(gridDim.x - gc) * 256;
-  for (i64 r = (i64)(blockIdx.x - gc) * 256 + threadIdx.x; r < R; r += stride) {
-    double acc = ld_f(rpv, dt, r);
-    for (i64 ct = 1; ct < CT; ++ct) acc += ld_f(rpv, dt, ct * R + r);
-    st_f(rout, dt, r, acc);
-  }
+  __shared__ double tile[PAIR_CTS * PAIR_ROWS];
+  const i64 blk = (i64)(blockIdx.x - gc);
+  if (dt == SPX_F32) finalize_pair_rows<float>((float*)tile, (const float*)rpv, CT, R, (float*)rout, blk);
+  else finalize_pair_rows<double>(tile, (const double*)rpv, CT, R, (double*)rout, blk);
 }
 
 extern "C" int spx_reduce_finalize_pair(int dtype, const void* col_part, int64_t P, int64_t n, void* col_out,
@@ -465,7 +500,7 @@ extern "C" int spx_reduce_finalize_pair(int dtype, const void* col_part, int64_t
   if (n == 0 && R == 0) return SPX_OK;
   if ((n > 0 && (!col_part || !col_out)) || (R > 0 && (!row_part || !row_out)))
     return set_err(SPX_EINVAL, "spx_reduce_finalize_pair: null pointer");
-  const unsigned gc = n > 0 ? finalize_grid(P, n) : 0, gr = R > 0 ? (unsigned)grid_for(R) : 0;
+  const unsigned gc = n > 0 ? finalize_grid(P, n) : 0, gr = (unsigned)((R + PAIR_ROWS - 1) / PAIR_ROWS);
   k_finalize_pair<<<gc + gr, 256, 0, S(stream)>>>(dtype, col_part, P, n, col_out, finalize_is_wide(P, n) ? 1 : 0, gc,
                                                   row_part, CT, R, row_out);
   LAUNCH_CHECK("spx_reduce_finalize_pair");
