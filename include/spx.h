@@ -36,7 +36,7 @@ extern "C" {
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
  * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
- * spx_als_plan, spx_als_solve */
+ * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp */
 
 /* error codes */
 #define SPX_OK 0
@@ -706,6 +706,40 @@ int spx_als_plan(int dtype, int64_t f, int64_t* fmax, int64_t* rows_per_block);
 int spx_als_solve(int dtype, int64_t m, int64_t n, int64_t f, int64_t nnz, const int64_t* rowptr, const int32_t* col,
                   const void* val, const void* Y, int64_t ldy, double lambda, void* X, int64_t ldx, int32_t* info,
                   void* stream);
+
+/* ------------------------------------------- all-pairs shortest paths
+ * Replaces the per-tile Cython Dijkstra of the reference's manifold learner
+ * (spartan/examples/util/graph_shortest_path.pyx, called from
+ * spartan/examples/sklearn/manifold/isomap.py:11-41) by the blocked
+ * Floyd-Warshall recurrence.
+ *
+ * spx_apsp: G (n x n, row-major, leading dimension ldg) holds edge weights: an
+ * off-diagonal G[i][j] is an edge i -> j of that weight iff it is finite and
+ * > 0; 0 and +inf both mean "no edge" and the diagonal is ignored.  With
+ * directed == 0 the edge between i and j is the smaller of the edges present
+ * in G[i][j] and G[j][i].  D (n x n, leading dimension ldd, D != G) receives
+ * the length of a shortest path from i to j, D[i][i] = 0, and `unreachable`
+ * cast to dtype where there is no path.  *info -- a device word the call
+ * clears first -- is 0, or -1 when any entry of G (the diagonal included) is
+ * negative, -inf or NaN; D is then unspecified, and nothing faults or loops.
+ * G is never written; bytes beyond column n of a row are neither read nor
+ * written.
+ *
+ * The matrix is cut into pivot blocks of edge b (spx_apsp_plan); per block
+ * one launch closes the diagonal tile, one updates the block row and block
+ * column, one updates every other tile by a (min, +) tile product.  All
+ * launches are ordered on `stream`; no host synchronisation, no graph
+ * capture, no atomics: a call's result is bitwise reproducible.  When every
+ * path sum is exact in dtype, the result is the exact one.
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a dtype code
+ * out of range, a negative n, an `unreachable` that is negative or NaN, a null
+ * pointer, a leading dimension below n or D == G; SPX_ENOTSUP for a dtype
+ * other than float32 / float64 or n > 2097120.  n == 0 is SPX_OK with no
+ * launch.  Additive since ABI 3. */
+int spx_apsp_plan(int dtype, int64_t* tile);
+int spx_apsp(int dtype, int directed, int64_t n, const void* G, int64_t ldg, void* D, int64_t ldd, double unreachable,
+             int32_t* info, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

@@ -29,8 +29,8 @@ from .layout import broadcast_strides, coalesce, reduce_view, contiguous_strides
 from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP_CODE, FILL_CONST, FILL_ARANGE,
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
-                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, als_plan, gemm_plan,
-                     GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
+                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, als_plan, apsp_plan,
+                     gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1298,6 +1298,40 @@ class HipBackend:
     self._call('spx_syevj', spx_dtype(dt), 0 if uplo == 'L' else 1, batch, n, _ptr(A), lda, stride_a, _ptr(W), n,
                _ptr(V), n, n * n, _ptr(info))
     return W, V, info
+
+  # ------------------------------------------------------- shortest paths
+  def apsp(self, G, directed=True, unreachable=float('inf')):
+    """(D, info): the all-pairs shortest path lengths of the edge-weight
+    matrix ``G`` (n, n) (spx_apsp).  An off-diagonal entry is an edge iff it is
+    finite and > 0 (0 and +inf: no edge; the diagonal is ignored); with
+    ``directed`` false the edge between i and j is the smaller of those present
+    in G[i, j] and G[j, i].  ``D`` is a new contiguous tensor of G's dtype with
+    ``unreachable`` where there is no path; ``info`` the one-element int32
+    device tensor, -1 when G holds a negative or NaN entry (D is then
+    unspecified); nothing here reads it.  ``G`` needs unit stride on its last
+    axis and a row stride of at least n, and is not written.  Asynchronous on
+    the current stream."""
+    import torch
+    if G.dim() != 2:
+      raise ValueError('apsp: G must be 2-d, got shape %s' % (tuple(G.shape),))
+    dt = np_dtype(G.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('apsp: G must be float32 / float64, not %s' % dt)
+    n = int(G.shape[1])
+    if int(G.shape[0]) != n:
+      raise ValueError('apsp: a square matrix is needed, got shape %s' % (tuple(G.shape),))
+    if n > 1 and (G.stride(1) != 1 or G.stride(0) < n):
+      raise ValueError('apsp: G needs unit stride on its last axis and a row stride of at least %d' % n)
+    unreachable = float(unreachable)
+    if not unreachable >= 0.0:
+      raise ValueError('apsp: unreachable = %r is negative or NaN' % unreachable)
+    ldg = int(G.stride(0)) if n > 1 else max(n, 1)
+    D = torch.empty((n, n), dtype=G.dtype, device=G.device)
+    info = torch.zeros((1,), dtype=torch.int32, device=G.device)
+    if n == 0:
+      return D, info
+    self._call('spx_apsp', spx_dtype(dt), 1 if directed else 0, n, _ptr(G), ldg, _ptr(D), n, unreachable, _ptr(info))
+    return D, info
 
   # --------------------------------------------------------------- sparse
   @staticmethod

@@ -133,6 +133,8 @@ def _signatures():
       'spx_csr_rowids': ([I64, I64, VP, I64, VP, VP], I),
       'spx_als_plan': ([I, I64, _I64P, _I64P], I),
       'spx_als_solve': ([I, I64, I64, I64, I64, VP, VP, VP, VP, I64, F64, VP, I64, VP, VP], I),
+      'spx_apsp_plan': ([I, _I64P], I),
+      'spx_apsp': ([I, I, I64, VP, I64, VP, I64, F64, VP, VP], I),
       'spx_comm_load': ([CP], I),
       'spx_comm_unique_id': ([VP, I64], I),
       'spx_comm_init': ([VP, I64, I, I, VPP], I),
@@ -386,6 +388,12 @@ def als_plan(dtype, f):
   from the library: the largest f the kernel holds in a wave's registers and
   the rows one workgroup solves (0 where f is outside 1 .. fmax)."""
   return _float_plan('als', 'ALS', dtype, 2, (f,), 'negative f = %d')
+
+
+def apsp_plan(dtype):
+  """The pivot-block edge b of spx_apsp for ``dtype``, from the library: the
+  matrix is processed in ceil(n / b) rounds of b x b tiles."""
+  return _float_plan('apsp', 'shortest-path', dtype, 1)[0]
 
 
 def __getattr__(name):
