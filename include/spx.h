@@ -36,7 +36,7 @@ extern "C" {
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
  * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
- * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp */
+ * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp, spx_fuzzy_plan, spx_fuzzy_step */
 
 /* error codes */
 #define SPX_OK 0
@@ -740,6 +740,50 @@ int spx_als_solve(int dtype, int64_t m, int64_t n, int64_t f, int64_t nnz, const
 int spx_apsp_plan(int dtype, int64_t* tile);
 int spx_apsp(int dtype, int directed, int64_t n, const void* G, int64_t ldg, void* D, int64_t ldd, double unreachable,
              int32_t* info, void* stream);
+
+/* ------------------------------------------------- fuzzy k-means step
+ * Replaces the expression graph of the reference's soft clustering driver
+ * (spartan/examples/fuzzy_kmeans.py), whose (n, k, d) and (n, k, k) broadcasts
+ * never fit, by one pass over the points.
+ *
+ * spx_fuzzy_step: points is N x D row-major with leading dimension ldp, in
+ * dtype (float32 / float64); centers is K x D float64, contiguous.  Per row i,
+ *
+ *   d_ij = sum_c (x_ic - c_jc)^2 + eps,
+ *   u_ij = (dmin_i / d_ij)^exponent / sum_j (dmin_i / d_ij)^exponent,
+ *
+ * which is 1 / sum_j (d_ij / d_il)^exponent without its overflow.  labels[i]
+ * (N int64, may be NULL) is the first index of the smallest d_ij; U (N x K in
+ * dtype, leading dimension ldu, may be NULL) receives u_ij; sums (K x D
+ * float64) and counts (K float64) receive sum_i u_ij^weight_power x_i and
+ * sum_i u_ij^weight_power -- overwritten when zero_first is set, else added to.
+ * points is never written; bytes beyond column D of a row are not read.
+ *
+ * float32 points: distances (difference form), memberships and the weighted
+ * sums within one row tile are float32; everything above a row tile -- the
+ * per-group partials, the counts and their reduction -- is float64.  float64
+ * points: float64 throughout.  No atomics and a fixed reduction order: a
+ * call's result is bitwise reproducible.  No load is wider than an element,
+ * so any base address and leading dimension are served by the same kernel.
+ *
+ * spx_fuzzy_plan (pure host): the rows of a row tile, the number of row groups
+ * (one persistent workgroup each), kmax (256) and the workspace bytes, which
+ * depend on dtype, D, K and groups only.  kmax, row_tile and groups are
+ * answered even where the call returns an error for K.
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a dtype code
+ * out of range, N < 0, D < 1, K < 1, an exponent, eps or weight_power that is
+ * not finite and > 0, ldp < D, ldu < K (with U), a null sums / counts /
+ * points / centers pointer, or a short or misaligned workspace; SPX_ENOTSUP
+ * for a dtype other than float32 / float64, K > kmax or D > 1048576.  N == 0
+ * reads no points pointer, launches nothing and clears sums / counts when
+ * zero_first is set.  Additive since ABI 3. */
+int spx_fuzzy_plan(int dtype, int64_t N, int64_t D, int64_t K, int64_t* row_tile, int64_t* groups, int64_t* kmax,
+                   size_t* workspace_bytes);
+int spx_fuzzy_step(int dtype, int64_t N, int64_t D, int64_t K, const void* points, int64_t ldp, const double* centers,
+                   double exponent, double eps, double weight_power, int64_t* labels, void* U, int64_t ldu,
+                   double* sums, double* counts, int zero_first, void* workspace, size_t workspace_bytes,
+                   void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

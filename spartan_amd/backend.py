@@ -30,7 +30,7 @@ from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
                      compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, als_plan, apsp_plan,
-                     gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
+                     fuzzy_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -376,6 +376,7 @@ class HipBackend:
     self._pair_last = None
     self._pair_memo = {}
     self._pair_own = False
+    self._fuzzy_ws = {}  # fuzzy_step workspaces by (dtype, D, K, device)
 
   # ---------------------------------------------------------------- utils
   def stream(self):
@@ -1332,6 +1333,59 @@ class HipBackend:
       return D, info
     self._call('spx_apsp', spx_dtype(dt), 1 if directed else 0, n, _ptr(G), ldg, _ptr(D), n, unreachable, _ptr(info))
     return D, info
+
+  # ---------------------------------------------------------- fuzzy k-means
+  def fuzzy_step(self, points, centers, exponent, eps, weight_power, want_labels, want_U, sums=None, counts=None):
+    """One fuzzy k-means step over ``points`` (N, D) float32 / float64 against
+    ``centers`` (K, D) float64 (spx_fuzzy_step): with d_j = |x - c_j|^2 + eps,
+    u_j = (dmin / d_j)^exponent / sum_j (dmin / d_j)^exponent per row.  Returns
+    ``(labels, U, sums, counts)``: labels (N,) int64, the first index of the
+    smallest d_j, with ``want_labels``, else None; U (N, K) in the points'
+    dtype with ``want_U``, else None; sums (K, D) and counts (K,) float64 of
+    u^weight_power x and u^weight_power.  Given ``sums`` and ``counts`` (both or
+    neither), the step is ADDED to them; otherwise they are new tensors.
+    ``points`` needs unit stride on its last axis and a row stride of at least
+    D; any base address is served.  Asynchronous on the current stream."""
+    import torch
+    if points.dim() != 2:
+      raise ValueError('fuzzy_step: points must be 2-d, got shape %s' % (tuple(points.shape),))
+    dt = np_dtype(points.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('fuzzy_step: points must be float32 / float64, not %s' % dt)
+    N, D = int(points.shape[0]), int(points.shape[1])
+    if centers.dim() != 2 or int(centers.shape[1]) != D or centers.dtype != torch.float64 or not centers.is_contiguous():
+      raise ValueError('fuzzy_step: centers must be a contiguous float64 (K, %d) tensor' % D)
+    K = int(centers.shape[0])
+    if D < 1 or K < 1:
+      raise ValueError('fuzzy_step: D = %d and K = %d must be at least 1' % (D, K))
+    if N > 1 and (points.stride(1) != 1 or points.stride(0) < D) or N == 1 and D > 1 and points.stride(1) != 1:
+      raise ValueError('fuzzy_step: points needs unit stride on its last axis and a row stride of at least %d' % D)
+    for name, v in (('exponent', exponent), ('eps', eps), ('weight_power', weight_power)):
+      if not (float(v) > 0.0 and np.isfinite(float(v))):
+        raise ValueError('fuzzy_step: %s = %r is not finite and > 0' % (name, v))
+    _rt, _g, kmax, need = fuzzy_plan(dt, N, D, K)
+    if K > kmax:
+      raise NotImplementedError('fuzzy_step: K = %d is above kmax = %d' % (K, kmax))
+    if (sums is None) != (counts is None):
+      raise ValueError('fuzzy_step: sums and counts are given together')
+    add = sums is not None
+    if add:
+      _dense('fuzzy_step: sums', sums, np.dtype(np.float64), K * D, '%d x %d elements' % (K, D))
+      _dense('fuzzy_step: counts', counts, np.dtype(np.float64), K, '%d elements' % K)
+    else:
+      sums = torch.empty((K, D), dtype=torch.float64, device=points.device)
+      counts = torch.empty((K,), dtype=torch.float64, device=points.device)
+    labels = torch.empty((N,), dtype=torch.int64, device=points.device) if want_labels else None
+    U = torch.empty((N, K), dtype=points.dtype, device=points.device) if want_U else None
+    key = (dt, D, K, points.device)
+    ws = self._fuzzy_ws.get(key)
+    if ws is None or ws.numel() < need:  # (kept per (dtype, D, K): its size does not depend on N)
+      ws = self._fuzzy_ws[key] = torch.empty((max(need, 16),), dtype=torch.uint8, device=points.device)
+    ldp = int(points.stride(0)) if N > 1 else D
+    self._call('spx_fuzzy_step', spx_dtype(dt), N, D, K, _ptr(points), ldp, _ptr(centers), float(exponent),
+               float(eps), float(weight_power), _ptr(labels), _ptr(U), K, _ptr(sums), _ptr(counts), 0 if add else 1,
+               _ptr(ws), ws.numel())
+    return labels, U, sums, counts
 
   # --------------------------------------------------------------- sparse
   @staticmethod

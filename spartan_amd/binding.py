@@ -135,6 +135,8 @@ def _signatures():
       'spx_als_solve': ([I, I64, I64, I64, I64, VP, VP, VP, VP, I64, F64, VP, I64, VP, VP], I),
       'spx_apsp_plan': ([I, _I64P], I),
       'spx_apsp': ([I, I, I64, VP, I64, VP, I64, F64, VP, VP], I),
+      'spx_fuzzy_plan': ([I, I64, I64, I64, _I64P, _I64P, _I64P, ctypes.POINTER(SZ)], I),
+      'spx_fuzzy_step': ([I, I64, I64, I64, VP, I64, VP, F64, F64, F64, VP, VP, I64, VP, VP, I, VP, SZ, VP], I),
       'spx_comm_load': ([CP], I),
       'spx_comm_unique_id': ([VP, I64], I),
       'spx_comm_init': ([VP, I64, I, I, VPP], I),
@@ -394,6 +396,28 @@ def apsp_plan(dtype):
   """The pivot-block edge b of spx_apsp for ``dtype``, from the library: the
   matrix is processed in ceil(n / b) rounds of b x b tiles."""
   return _float_plan('apsp', 'shortest-path', dtype, 1)[0]
+
+
+def fuzzy_plan(dtype, N, D, K):
+  """(row_tile, groups, kmax, workspace bytes) of spx_fuzzy_step for (N, D)
+  points of ``dtype`` and K centres, from the library: the rows over which the
+  float32 accumulators of a group live, the number of row groups (persistent
+  workgroups), the largest K and the workspace, which depends on dtype, D, K
+  and groups only.  For K above kmax the first three are still answered and
+  the workspace is None."""
+  dt = np.dtype(dtype)
+  if dt not in _FLOATS:
+    raise TypeError('fuzzy_plan: dtype %s has no fuzzy k-means kernel (float32 / float64)' % dt)
+  N, D, K = int(N), int(D), int(K)
+  if N < 0 or D < 1 or K < 1:
+    raise ValueError('fuzzy_plan: bad sizes (N %d, D %d, K %d)' % (N, D, K))
+  rt, g, kmax = (ctypes.c_int64(0) for _ in range(3))
+  nbytes = ctypes.c_size_t(0)
+  rc = load_library().spx_fuzzy_plan(spx_dtype(dt), N, D, K, ctypes.byref(rt), ctypes.byref(g), ctypes.byref(kmax),
+                                     ctypes.byref(nbytes))
+  if rc != 0 and K <= kmax.value:
+    _check(rc, 'spx_fuzzy_plan')
+  return int(rt.value), int(g.value), int(kmax.value), (int(nbytes.value) if rc == 0 else None)
 
 
 def __getattr__(name):

@@ -9,6 +9,7 @@ from .builtins import (abs, add, arange, argmax, argmin, astype, bincount, conca
 from .dot import dot
 from .eigh import eigh, eigvalsh
 from .filter import compress, take
+from .fuzzy import fuzzy_assign, fuzzy_membership
 from .graph import shortest_path
 from .join import map2, outer
 from .linalg import cho_solve, cholesky, solve_triangular
