@@ -36,7 +36,8 @@ extern "C" {
  * spx_potrf_plan, spx_potrf_workspace, spx_potrf, spx_trsm_workspace, spx_trsm, spx_syrk,
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
  * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
- * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp, spx_fuzzy_plan, spx_fuzzy_step */
+ * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp, spx_fuzzy_plan, spx_fuzzy_step,
+ * spx_gesvj_plan, spx_gesvj */
 
 /* error codes */
 #define SPX_OK 0
@@ -615,6 +616,60 @@ int spx_orgqr(int dtype, int64_t m, int64_t n, void* workspace, size_t workspace
 int spx_syevj_plan(int dtype, int64_t* nmax, int64_t* sweep_max);
 int spx_syevj(int dtype, int uplo, int64_t batch, int64_t n, const void* A, int64_t lda, int64_t stride_a, void* W,
               int64_t stride_w, void* V, int64_t ldv, int64_t stride_v, int32_t* info, void* stream);
+
+/* ------------------------------------------- dense SVD (one-sided Jacobi)
+ * The reduced singular value decomposition A = U diag(S) Vt of `batch`
+ * row-major m x n matrices with m >= n, what np.linalg.svd(full_matrices=False)
+ * computes for an (..., m, n) array, by the one-sided (Hestenes) Jacobi method:
+ * one workgroup per matrix, which never leaves LDS, the grid over the batch.
+ * The method rotates the columns of A itself and never forms A^T A, so small
+ * singular values are resolved to high relative accuracy.  float32 and float64
+ * only (another dtype: SPX_ENOTSUP); asynchronous on the stream; no workspace,
+ * no atomics.
+ *
+ * The plan call returns SPX_OK and writes the column limit *nmax of the dtype
+ * (the largest multiple of 32 for which a square matrix fits: 128 for float32,
+ * 96 for float64), the row limit *mmax for n columns (the largest m whose
+ * working copy, n columns of m | 1, fits the 160 KiB one workgroup may declare
+ * beside V, n columns of n | 1; 0 for n > nmax) and *sweep_max (64); any pointer
+ * may be NULL.  The plan describes jobu == 1; with jobu == 0 V is not held and
+ * spx_gesvj accepts the correspondingly larger m.
+ *
+ * Matrix b is A + b stride_a with leading dimension lda >= n; A is read once
+ * and never written.  S + b stride_s receives the n singular values, descending
+ * and non-negative.  With jobu == 1, U + b stride_u (m x n, leading dimension
+ * ldu) receives the left singular vectors as columns and Vt + b stride_vt
+ * (n x n, leading dimension ldvt) the right ones as rows, in the same order;
+ * with jobu == 0 only S is computed and U and Vt must be NULL.  In every row of
+ * Vt the entry of largest magnitude (the first on a tie) is positive; the
+ * column of U carries the sign.  For an exactly zero singular value the column
+ * of U is exactly zero (LAPACK gesvj's contract: only the columns of nonzero
+ * singular values are orthonormal); two equal columns and a zero column of A
+ * give such a zero.  A = U diag(S) Vt and Vt Vt^T = I hold regardless.
+ * info[b] is the number of sweeps used (>= 0; 0 for the zero matrix and for
+ * n = 1), or -1 when matrix b did not converge within sweep_max sweeps or holds
+ * a non-finite value: its outputs are then filled with NaN and the other
+ * matrices of the batch are not affected.  Bytes beyond column n of any row of
+ * A, U and Vt, and beyond entry n of S, are neither read nor written.
+ *
+ * The matrix is scaled by the power of two of its largest magnitude (exact); a
+ * sweep is the m' - 1 rounds of the round-robin ordering of spx_syevj over the
+ * m' = n + (n & 1) columns; the pair (p, q) is rotated iff a_pp > 0, a_qq > 0
+ * and |a_pq| > sqrt(m) u sqrt(a_pp) sqrt(a_qq), the three dot products formed
+ * anew in every round in the data's dtype; a sweep without a rotation ends the
+ * iteration.  The workgroup size depends on (m, n) alone: a matrix gives the
+ * same bits wherever it stands in a batch and whatever the batch size.
+ *
+ * Arguments are checked before any device work: SPX_EINVAL for a null pointer
+ * (or a non-null U / Vt with jobu == 0), a jobu other than 0 / 1, a negative
+ * size, m < n, a leading dimension below n, a negative stride_a or (batch > 1)
+ * output strides that let two matrices overlap; SPX_ENOTSUP for n > nmax,
+ * m > mmax or batch >= 2^31; batch == 0 or n == 0 is SPX_OK with no launch.
+ * Additive since ABI 3. */
+int spx_gesvj_plan(int dtype, int64_t n, int64_t* nmax, int64_t* mmax, int64_t* sweep_max);
+int spx_gesvj(int dtype, int jobu, int64_t batch, int64_t m, int64_t n, const void* A, int64_t lda, int64_t stride_a,
+              void* U, int64_t ldu, int64_t stride_u, void* S, int64_t stride_s, void* Vt, int64_t ldvt,
+              int64_t stride_vt, int32_t* info, void* stream);
 
 /* ------------------------------------------------- sparse (CSR) x dense
  * Replaces the scipy.sparse branches of the reference's dot

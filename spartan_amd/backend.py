@@ -29,8 +29,8 @@ from .layout import broadcast_strides, coalesce, reduce_view, contiguous_strides
 from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP_CODE, FILL_CONST, FILL_ARANGE,
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
-                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, csrmm_plan, als_plan, apsp_plan,
-                     fuzzy_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
+                     compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, gesvj_plan, csrmm_plan, als_plan,
+                     apsp_plan, fuzzy_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1299,6 +1299,50 @@ class HipBackend:
     self._call('spx_syevj', spx_dtype(dt), 0 if uplo == 'L' else 1, batch, n, _ptr(A), lda, stride_a, _ptr(W), n,
                _ptr(V), n, n * n, _ptr(info))
     return W, V, info
+
+  # ------------------------------------------------------------------- svd
+  def gesvj(self, A, compute_uv=True):
+    """(U, S, Vt, info) of ``A``, (m, n) or a batch (B, m, n) with m >= n
+    (spx_gesvj): the reduced SVD A = U diag(S) Vt with S (n,) / (B, n)
+    descending, U (.., m, n) and Vt (.., n, n); every row of Vt has its entry of
+    largest magnitude positive, and the column of U of an exactly zero singular
+    value is exactly zero.  With ``compute_uv`` false only S is computed and U
+    and Vt are None.  ``info`` is the int32 device tensor (one entry per matrix)
+    of the sweeps used, -1 where a matrix did not converge or is not finite
+    (its outputs are NaN); nothing here reads it.  ``A`` needs unit stride on
+    its last axis and a row stride of at least n, any batch stride, and is not
+    written.  Asynchronous on the current stream."""
+    import torch
+    if A.dim() not in (2, 3):
+      raise ValueError('gesvj: A must be 2-d or 3-d, got shape %s' % (tuple(A.shape),))
+    dt = np_dtype(A.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('gesvj: A must be float32 / float64, not %s' % dt)
+    m, n = int(A.shape[-2]), int(A.shape[-1])
+    if m < n:
+      raise ValueError('gesvj: tall or square matrices are needed (m >= n), got shape %s' % (tuple(A.shape),))
+    nmax, mmax, _ = gesvj_plan(dt, n)
+    if n > nmax:
+      raise ValueError('gesvj: n = %d is above the limit %d for %s' % (n, nmax, dt))
+    if n > 0 and m > mmax:
+      raise ValueError('gesvj: m = %d is above the limit %d for n = %d, %s' % (m, mmax, n, dt))
+    batch = int(A.shape[0]) if A.dim() == 3 else 1
+    if batch > 0 and n > 0 and ((n > 1 and A.stride(-1) != 1) or (m > 1 and A.stride(-2) < n)):
+      raise ValueError('gesvj: A needs unit stride on its last axis and a row stride of at least %d' % n)
+    lda = int(A.stride(-2)) if m > 1 else max(n, 1)
+    stride_a = int(A.stride(0)) if A.dim() == 3 and batch > 1 else 0
+    lead = tuple(A.shape[:-2])
+    S = torch.empty(lead + (n,), dtype=A.dtype, device=A.device)
+    U = Vt = None
+    if compute_uv:
+      U = torch.empty(lead + (m, n), dtype=A.dtype, device=A.device)
+      Vt = torch.empty(lead + (n, n), dtype=A.dtype, device=A.device)
+    info = torch.zeros((batch,), dtype=torch.int32, device=A.device)
+    if batch == 0 or n == 0:
+      return U, S, Vt, info
+    self._call('spx_gesvj', spx_dtype(dt), 1 if compute_uv else 0, batch, m, n, _ptr(A), lda, stride_a, _ptr(U), n,
+               m * n, _ptr(S), n, _ptr(Vt), n, n * n, _ptr(info))
+    return U, S, Vt, info
 
   # ------------------------------------------------------- shortest paths
   def apsp(self, G, directed=True, unreachable=float('inf')):

@@ -126,6 +126,8 @@ def _signatures():
       'spx_orgqr': ([I, I64, I64, VP, SZ, VP, I64, VP, I64, VP], I),
       'spx_syevj_plan': ([I, _I64P, _I64P], I),
       'spx_syevj': ([I, I, I64, I64, VP, I64, I64, VP, I64, VP, I64, I64, VP, VP], I),
+      'spx_gesvj_plan': ([I, I64, _I64P, _I64P, _I64P], I),
+      'spx_gesvj': ([I, I, I64, I64, I64, VP, I64, I64, VP, I64, I64, VP, I64, VP, I64, I64, VP, VP], I),
       'spx_csrmm_plan': ([I, I64, I64, I64, _I64P, _I64P, _I64P], I),
       'spx_csrmm_workspace': ([I, I64, I64, I64], I64),
       'spx_csrmm': ([I, I64, I64, I64, I64, VP, VP, VP, VP, I64, VP, I64, F64, F64, I64, VP, SZ, I, VP], I),
@@ -375,6 +377,13 @@ def syevj_plan(dtype):
   """(nmax, sweep_max) of spx_syevj for ``dtype``, from the library: the
   largest n one workgroup holds in LDS and the bound on the sweeps."""
   return _float_plan('syevj', 'eigen-solver', dtype, 2)
+
+
+def gesvj_plan(dtype, n):
+  """(nmax, mmax, sweep_max) of spx_gesvj for ``n`` columns of ``dtype``, from
+  the library: the column limit, the most rows one workgroup holds in LDS beside
+  the n x n V (0 where n is above the limit) and the bound on the sweeps."""
+  return _float_plan('gesvj', 'SVD', dtype, 3, (n,), 'negative n = %d')
 
 
 def csrmm_plan(dtype, m, nnz, p):

@@ -937,6 +937,9 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
 // ===================================== batched Jacobi eigen-solver (eigh)
 #include "eigh_kernels.h"
 
+// ============================= batched one-sided Jacobi SVD (svd / pinv)
+#include "svd_kernels.h"
+
 // ============================================== sparse (CSR) x dense, todense
 #include "sparse_kernels.h"
 

@@ -23,6 +23,7 @@ from .scan import scan
 from .slice import slice_expr
 from .sort import argpartition, argsort, partition, sort
 from .sparse import sparse_diagonal, sparse_empty, sparse_rand, sparse_transpose, todense
+from .svd import pinv, svd, svdvals
 from .topk import argtopk, topk
 from .transpose import transpose
 from .write_array import from_file, from_numpy, write
