@@ -37,7 +37,7 @@ extern "C" {
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
  * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
  * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp, spx_fuzzy_plan, spx_fuzzy_step,
- * spx_gesvj_plan, spx_gesvj */
+ * spx_gesvj_plan, spx_gesvj, spx_nbody_plan, spx_nbody_accel */
 
 /* error codes */
 #define SPX_OK 0
@@ -839,6 +839,50 @@ int spx_fuzzy_step(int dtype, int64_t N, int64_t D, int64_t K, const void* point
                    double exponent, double eps, double weight_power, int64_t* labels, void* U, int64_t ldu,
                    double* sums, double* counts, int zero_first, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* ------------------------------------------- n-body direct summation
+ * Replaces the expression graph of the reference's n-body driver
+ * (spartan/examples/nbody.py move()), a dozen (n, n) arrays per time step, by
+ * one all-pairs kernel that reads 4 n values and writes 3 n.
+ *
+ * spx_nbody_accel: tx, ty, tz (n_tgt) are the targets' coordinates, sx, sy,
+ * sz, sm (n_src) the sources' coordinates and masses, all contiguous vectors
+ * of dtype (float32 / float64); the targets may be the sources.  For target j
+ *
+ *   d_i = s_i - t_j,  r_i = |d_i|,  r_i = rmin where r_i < rmin,
+ *   a_j = sum_i G sm_i d_i / r_i^3
+ *
+ * is stored to ax, ay, az (n_tgt, dtype).  A pair at distance 0 contributes
+ * exactly 0 when rmin > 0 (d = 0, r = rmin), so a target that is one of the
+ * sources needs no index test; with rmin == 0 such a pair is 0 / 0 = NaN.
+ * r < rmin is false for NaN: a NaN coordinate or mass makes every output NaN.
+ * r^3 is never formed ((G m) / r / r / r * d), so float32 data with G m near
+ * 1e20 and r near 1e14 stays in range; r^2 itself must not overflow dtype.
+ *
+ * A workgroup owns tgt_per_block targets and one of `splits` contiguous source
+ * ranges.  splits == 0 takes spx_nbody_plan's choice (enough workgroups for
+ * the CUs, no range shorter than 128 sources); a positive value forces it.
+ * With splits > 1 the float64 partials [split][3][n_tgt] go to the workspace
+ * and a second kernel adds them in ascending split order.  Sums of more than
+ * 32 terms are carried in float64 in both dtypes.  No atomics: the same
+ * inputs and split give bitwise identical outputs.
+ *
+ * spx_nbody_plan (pure host): *splits is read (NULL or 0: choose; positive:
+ * forced) and receives the value used; workspace_bytes the bytes spx_nbody_accel
+ * needs for it (0 for one split).
+ *
+ * Checked before any device work: SPX_EINVAL for a dtype code out of range, a
+ * negative size, splits outside 0 .. 1024, a G that is not finite, an rmin
+ * that is not finite and >= 0, a null pointer among the arrays that are read
+ * or written, or a short or misaligned workspace; SPX_ENOTSUP for a dtype
+ * other than float32 / float64, n_tgt above 2^31 - 1 workgroups' worth or
+ * n_src above 2^48.  n_tgt == 0 launches nothing; n_src == 0 writes zeros.
+ * Additive since ABI 3. */
+int spx_nbody_plan(int dtype, int64_t n_tgt, int64_t n_src, int64_t* tgt_per_block, int64_t* splits,
+                   size_t* workspace_bytes);
+int spx_nbody_accel(int dtype, int64_t n_tgt, const void* tx, const void* ty, const void* tz, int64_t n_src,
+                    const void* sx, const void* sy, const void* sz, const void* sm, double G, double rmin, void* ax,
+                    void* ay, void* az, int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

@@ -30,7 +30,8 @@ from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
                      compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, gesvj_plan, csrmm_plan, als_plan,
-                     apsp_plan, fuzzy_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit, _ptr)
+                     apsp_plan, fuzzy_plan, nbody_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit,
+                     _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -377,6 +378,7 @@ class HipBackend:
     self._pair_memo = {}
     self._pair_own = False
     self._fuzzy_ws = {}  # fuzzy_step workspaces by (dtype, D, K, device)
+    self._nbody_ws = {}  # nbody_accel workspaces (the float64 partials of a split) by device
 
   # ---------------------------------------------------------------- utils
   def stream(self):
@@ -1431,6 +1433,36 @@ class HipBackend:
                _ptr(ws), ws.numel())
     return labels, U, sums, counts
 
+  # ------------------------------------------------------------------ n-body
+  def nbody_accel(self, tx, ty, tz, sx, sy, sz, sm, G, rmin, splits=None):
+    """``(ax, ay, az)``: the accelerations of the targets ``tx, ty, tz`` under
+    the sources ``sx, sy, sz`` of mass ``sm`` (spx_nbody_accel): for target j,
+    sum_i G sm_i (s_i - t_j) / r_i^3 with r_i = max(|s_i - t_j|, rmin).  All
+    seven are contiguous 1-d tensors of one dtype (float32 / float64), the
+    targets of one length and the sources of one length; the targets may be the
+    sources.  The outputs are new tensors of the targets' length and dtype
+    (zeros without sources).  ``splits``: None for the library's choice of
+    source ranges, a positive number to force it.  Asynchronous on the current
+    stream."""
+    import torch
+    _nbody_args('nbody_accel', (tx, ty, tz), (sx, sy, sz, sm), G, rmin)
+    dt = np_dtype(tx.dtype)
+    n_tgt, n_src = int(tx.numel()), int(sx.numel())
+    splits = 0 if splits is None else int(splits)
+    if splits < 0:
+      raise ValueError('nbody_accel: splits = %d is negative' % splits)
+    ax, ay, az = (torch.empty((n_tgt,), dtype=tx.dtype, device=tx.device) for _ in range(3))
+    if n_tgt == 0:
+      return ax, ay, az
+    _tpb, use, need = nbody_plan(dt, n_tgt, n_src, splits)
+    ws = self._nbody_ws.get(tx.device)
+    if need and (ws is None or ws.numel() < need):  # (one per device, grown to the largest split seen)
+      ws = self._nbody_ws[tx.device] = torch.empty((need,), dtype=torch.uint8, device=tx.device)
+    self._call('spx_nbody_accel', spx_dtype(dt), n_tgt, _ptr(tx), _ptr(ty), _ptr(tz), n_src, _ptr(sx), _ptr(sy),
+               _ptr(sz), _ptr(sm), float(G), float(rmin), _ptr(ax), _ptr(ay), _ptr(az), use,
+               _ptr(ws if need else None), ws.numel() if need else 0)
+    return ax, ay, az
+
   # --------------------------------------------------------------- sparse
   @staticmethod
   def _csr(name, rowptr, col, val, n):
@@ -1582,6 +1614,27 @@ def _dense(what, t, dtype, numel, size):
   elements (``size``: how the message words that count)."""
   if np_dtype(t.dtype) != dtype or not t.is_contiguous() or t.numel() != numel:
     raise ValueError('%s must be a contiguous %s tensor of %s' % (what, dtype, size))
+
+
+def _nbody_args(who, targets, sources, G, rmin):
+  """ValueError unless the n-body operands are contiguous 1-d tensors of one
+  float32 / float64 dtype, of one length within each group, with a finite G
+  and a finite rmin >= 0."""
+  dt = np_dtype(targets[0].dtype)
+  if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    raise ValueError('%s: the arrays must be float32 / float64, not %s' % (who, dt))
+  for name, group in (('targets', targets), ('sources', sources)):
+    for t in group:
+      if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError('%s: the %s must be contiguous 1-d tensors, got shape %s' % (who, name, tuple(t.shape)))
+      if np_dtype(t.dtype) != dt:
+        raise ValueError('%s: one dtype is needed, got %s and %s' % (who, dt, np_dtype(t.dtype)))
+      if t.numel() != group[0].numel():
+        raise ValueError('%s: the %s have unequal lengths %d and %d' % (who, name, group[0].numel(), t.numel()))
+  if not np.isfinite(float(G)):
+    raise ValueError('%s: G = %r is not finite' % (who, G))
+  if not (float(rmin) >= 0.0 and np.isfinite(float(rmin))):
+    raise ValueError('%s: rmin = %r is not finite and >= 0' % (who, rmin))
 
 
 def _vec_aligned(t, strides, cls, V):

@@ -139,6 +139,8 @@ def _signatures():
       'spx_apsp': ([I, I, I64, VP, I64, VP, I64, F64, VP, VP], I),
       'spx_fuzzy_plan': ([I, I64, I64, I64, _I64P, _I64P, _I64P, ctypes.POINTER(SZ)], I),
       'spx_fuzzy_step': ([I, I64, I64, I64, VP, I64, VP, F64, F64, F64, VP, VP, I64, VP, VP, I, VP, SZ, VP], I),
+      'spx_nbody_plan': ([I, I64, I64, _I64P, _I64P, ctypes.POINTER(SZ)], I),
+      'spx_nbody_accel': ([I, I64, VP, VP, VP, I64, VP, VP, VP, VP, F64, F64, VP, VP, VP, I64, VP, SZ, VP], I),
       'spx_comm_load': ([CP], I),
       'spx_comm_unique_id': ([VP, I64], I),
       'spx_comm_init': ([VP, I64, I, I, VPP], I),
@@ -427,6 +429,25 @@ def fuzzy_plan(dtype, N, D, K):
   if rc != 0 and K <= kmax.value:
     _check(rc, 'spx_fuzzy_plan')
   return int(rt.value), int(g.value), int(kmax.value), (int(nbytes.value) if rc == 0 else None)
+
+
+def nbody_plan(dtype, n_tgt, n_src, splits=0):
+  """(tgt_per_block, splits, workspace bytes) of spx_nbody_accel for ``n_tgt``
+  targets against ``n_src`` sources of ``dtype``, from the library: the targets
+  one workgroup owns, the contiguous source ranges the work is cut into
+  (``splits`` 0: the library's choice; positive: forced) and the bytes of the
+  float64 partials (0 for one range)."""
+  dt = np.dtype(dtype)
+  if dt not in _FLOATS:
+    raise TypeError('nbody_plan: dtype %s has no n-body kernel (float32 / float64)' % dt)
+  n_tgt, n_src, splits = int(n_tgt), int(n_src), int(splits)
+  if n_tgt < 0 or n_src < 0:
+    raise ValueError('nbody_plan: negative size (n_tgt %d, n_src %d)' % (n_tgt, n_src))
+  tpb, s = ctypes.c_int64(0), ctypes.c_int64(splits)
+  nbytes = ctypes.c_size_t(0)
+  _check(load_library().spx_nbody_plan(spx_dtype(dt), n_tgt, n_src, ctypes.byref(tpb), ctypes.byref(s),
+                                       ctypes.byref(nbytes)), 'spx_nbody_plan')
+  return int(tpb.value), int(s.value), int(nbytes.value)
 
 
 def __getattr__(name):

@@ -15,6 +15,7 @@ from .join import map2, outer
 from .linalg import cho_solve, cholesky, solve_triangular
 from .map import map
 from .map_with_location import map_with_location, region_map
+from .nbody import nbody_accel
 from .ndarray import ndarray
 from .qr import qr
 from .reduce import reduce
