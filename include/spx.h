@@ -37,7 +37,8 @@ extern "C" {
  * spx_geqr_plan, spx_geqr_workspace, spx_geqr, spx_orgqr, spx_csrmm_plan, spx_csrmm_workspace,
  * spx_csrmm, spx_csr_todense, spx_syevj_plan, spx_syevj, spx_gemm_plan, spx_csr_rowids,
  * spx_als_plan, spx_als_solve, spx_apsp_plan, spx_apsp, spx_fuzzy_plan, spx_fuzzy_step,
- * spx_gesvj_plan, spx_gesvj, spx_nbody_plan, spx_nbody_accel */
+ * spx_gesvj_plan, spx_gesvj, spx_nbody_plan, spx_nbody_accel, spx_pairwise_plan,
+ * spx_pairwise */
 
 /* error codes */
 #define SPX_OK 0
@@ -883,6 +884,61 @@ int spx_nbody_plan(int dtype, int64_t n_tgt, int64_t n_src, int64_t* tgt_per_blo
 int spx_nbody_accel(int dtype, int64_t n_tgt, const void* tx, const void* ty, const void* tz, int64_t n_src,
                     const void* sx, const void* sy, const void* sz, const void* sm, double G, double rmin, void* ax,
                     void* ay, void* az, int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------ pairwise kernels
+ * The two fixed computations behind the `shuffle` calls of the reference's
+ * spectral clustering (spartan/examples/spectral_clustering.py: the Python
+ * double loop of _row_similarity_mapper and the scaling of _laplacian_mapper),
+ * and a cdist / pairwise_kernels primitive of its own.
+ *
+ * spx_pairwise: X is (n, d) with leading dimension ldx, Y is (m, d) with
+ * leading dimension ldy, both row-major of dtype (float32 / float64); Y may be
+ * X.  With s_ij = sum_k (x_ik - y_jk)^2 the value a_ij is */
+#define SPX_PAIR_SQEUCLIDEAN 0 /* s_ij                      */
+#define SPX_PAIR_EUCLIDEAN 1   /* sqrt(s_ij)                */
+#define SPX_PAIR_MANHATTAN 2   /* sum_k |x_ik - y_jk|       */
+#define SPX_PAIR_RBF 3         /* exp(-gamma s_ij)          */
+/* evaluated in the difference form, k = 0 .. d - 1 in one order for every
+ * element: equal rows give exactly 0 (rbf: exactly 1), and with Y == X the
+ * result is bitwise symmetric.  gamma is read by rbf only.
+ *
+ *   row_scale (n), col_scale (m): both NULL or both given; the value becomes
+ *     a_ij * (row_scale_i * col_scale_j), the product of the scales first;
+ *   out (n, m; leading dimension ldo; may be NULL) receives the values;
+ *     with diag_col0 >= 0 element (i, diag_col0 + i) receives diag_value
+ *     instead (a row slab that starts at global row diag_col0);
+ *   row_sums (n; may be NULL) receives sum_j of the values -- the computed
+ *     ones, not diag_value.
+ *
+ * A workgroup owns `tile` rows and one of `splits` column ranges of whole
+ * tiles, which it walks in ascending order, d staged k_chunk values at a time.
+ * Sums above one tile are carried in float64.  splits == 0 takes
+ * spx_pairwise_plan's choice (enough workgroups for the CUs, no range shorter
+ * than four tiles); a positive value forces it.  With row_sums and splits > 1
+ * the float64 partials [split][n] go to the workspace and a second kernel adds
+ * them in ascending split order.  No atomics: the same inputs and split give
+ * bitwise identical outputs.  A NaN coordinate makes that point's row (in X)
+ * or column (in Y) NaN and nothing else of out; rbf of an overflowing
+ * gamma * s is 0.
+ *
+ * spx_pairwise_plan (pure host): tile and k_chunk receive the kernel's tile
+ * edge and k-chunk; *splits is read (NULL or 0: choose; positive: forced) and
+ * receives the value used; workspace_bytes the bytes a call with row_sums needs
+ * for it (0 for one split; a call without row_sums needs none).
+ *
+ * Checked before any device work: SPX_EINVAL for a dtype code out of range, a
+ * negative size, splits outside 0 .. 1024, an unknown metric, d < 1, a gamma
+ * that is not finite and >= 0, out and row_sums both NULL, one scale without
+ * the other, ldx or ldy below d, ldo below m, a null X or Y, or a short or
+ * misaligned workspace; SPX_ENOTSUP for a dtype other than float32 / float64,
+ * n above 2^31 - 1 workgroups' worth or m above 2^48.  n == 0 or m == 0
+ * succeeds and launches nothing.  Additive since ABI 3. */
+int spx_pairwise_plan(int dtype, int64_t n, int64_t m, int64_t* tile, int64_t* k_chunk, int64_t* splits,
+                      size_t* workspace_bytes);
+int spx_pairwise(int dtype, int metric, int64_t n, int64_t m, int64_t d, const void* X, int64_t ldx, const void* Y,
+                 int64_t ldy, double gamma, void* out, int64_t ldo, void* row_sums, const void* row_scale,
+                 const void* col_scale, int64_t diag_col0, double diag_value, int64_t splits, void* workspace,
+                 size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ automatic tiling */
 /* Host-only (no device work, callable without a GPU): the node choice on the

@@ -30,8 +30,8 @@ from .binding import (LIB_PATH, SPX_BOOL, SPX_I32, SPX_I64, SPX_F32, SPX_F64, OP
                      FILL_UNIFORM, FILL_NORMAL, EXPORTED, SCAN_CHUNK, SORT_LDS_MAX, SORT_TILE, spx_dtype, torch_dtype,
                      np_dtype, load_library, mincost_tiling, scan_dtypes, scan_plan, sort_plan, topk_plan, knn_plan,
                      compact_tile, stencil_plan, potrf_plan, geqr_plan, syevj_plan, gesvj_plan, csrmm_plan, als_plan,
-                     apsp_plan, fuzzy_plan, nbody_plan, gemm_plan, GEMM_KERNELS, current_stream, _arr, _check, _k_limit,
-                     _ptr)
+                     apsp_plan, fuzzy_plan, nbody_plan, pairwise_plan, PAIR_METRICS, gemm_plan, GEMM_KERNELS,
+                     current_stream, _arr, _check, _k_limit, _ptr)
 from .util import prod
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -379,6 +379,7 @@ class HipBackend:
     self._pair_own = False
     self._fuzzy_ws = {}  # fuzzy_step workspaces by (dtype, D, K, device)
     self._nbody_ws = {}  # nbody_accel workspaces (the float64 partials of a split) by device
+    self._pairwise_ws = {}  # pairwise workspaces (the float64 row-sum partials of a split) by device
 
   # ---------------------------------------------------------------- utils
   def stream(self):
@@ -1462,6 +1463,94 @@ class HipBackend:
                _ptr(sz), _ptr(sm), float(G), float(rmin), _ptr(ax), _ptr(ay), _ptr(az), use,
                _ptr(ws if need else None), ws.numel() if need else 0)
     return ax, ay, az
+
+  # ------------------------------------------------------- pairwise kernels
+  def pairwise(self, X, Y, metric, gamma, out=None, row_sums=None, row_scale=None, col_scale=None, diag_col0=-1,
+               diag_value=0.0, splits=None):
+    """``(out, row_sums)`` of spx_pairwise: for the (n, d) rows of ``X`` and
+    the (m, d) rows of ``Y`` (2-d tensors of one float32 / float64 dtype with
+    unit column stride: column slices of wider tensors are accepted, and Y may
+    be X) the values a_ij of ``metric`` ('sqeuclidean', 'euclidean',
+    'manhattan', 'rbf' = exp(-gamma s_ij)), times ``row_scale[i] *
+    col_scale[j]`` where the two (n,) / (m,) vectors are given.  ``out``: True
+    for a new (n, m) tensor, a tensor (unit column stride) to fill, None / False
+    for none; with ``diag_col0 >= 0`` its element (i, diag_col0 + i) is
+    ``diag_value``.  ``row_sums``: True for a new (n,) tensor of sum_j of the
+    computed values, a contiguous tensor to fill, None / False for none.  At
+    least one of the two is wanted.  ``splits``: None for the library's choice
+    of column ranges, a positive number to force it.  Asynchronous on the
+    current stream."""
+    import torch
+    who = 'pairwise'
+    for name, t in (('X', X), ('Y', Y)):
+      if t.dim() != 2:
+        raise ValueError('%s: %s must be 2-d, got shape %s' % (who, name, tuple(t.shape)))
+    dt = np_dtype(X.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError('%s: X must be float32 / float64, not %s' % (who, dt))
+    if np_dtype(Y.dtype) != dt:
+      raise ValueError('%s: Y has dtype %s, X has %s: one dtype is needed' % (who, np_dtype(Y.dtype), dt))
+    n, d = (int(v) for v in X.shape)
+    m = int(Y.shape[0])
+    if int(Y.shape[1]) != d:
+      raise ValueError('%s: Y has %d features, X has %d' % (who, int(Y.shape[1]), d))
+    if d < 1:
+      raise ValueError('%s: X has no features (d = 0)' % who)
+    if metric not in PAIR_METRICS:
+      raise ValueError('%s: metric %r is not one of %s' % (who, metric, sorted(PAIR_METRICS)))
+    gamma = float(gamma)
+    if not (gamma >= 0.0 and np.isfinite(gamma)):
+      raise ValueError('%s: gamma = %r is not finite and >= 0' % (who, gamma))
+    splits = 0 if splits is None else int(splits)
+    if splits < 0:
+      raise ValueError('%s: splits = %d is negative' % (who, splits))
+
+    def rows_of(name, t, rows, cols):  # the leading dimension of a 2-d operand with unit column stride
+      if cols > 1 and t.stride(1) != 1:
+        raise ValueError('%s: %s must have unit column stride, got strides %s' % (who, name, tuple(t.stride())))
+      ld = int(t.stride(0)) if rows > 1 else cols
+      if ld < cols:
+        raise ValueError('%s: the rows of %s overlap (row stride %d, %d columns)' % (who, name, ld, cols))
+      return ld
+
+    ldx, ldy = rows_of('X', X, n, d), rows_of('Y', Y, m, d)
+    if (row_scale is None) != (col_scale is None):
+      raise ValueError('%s: row_scale and col_scale go together (both or neither)' % who)
+    for name, t, size in (('row_scale', row_scale, n), ('col_scale', col_scale, m)):
+      if t is not None:
+        _dense('%s: %s' % (who, name), t, dt, size, '%d elements' % size)
+    if out is None or out is False:
+      out = None
+    elif out is True:
+      out = torch.empty((n, m), dtype=X.dtype, device=X.device)
+    elif out.dim() != 2 or tuple(out.shape) != (n, m) or np_dtype(out.dtype) != dt:
+      raise ValueError('%s: out must be a (%d, %d) %s tensor, got %s %s' % (who, n, m, dt, tuple(out.shape),
+                                                                           np_dtype(out.dtype)))
+    if row_sums is None or row_sums is False:
+      row_sums = None
+    elif row_sums is True:
+      row_sums = torch.empty((n,), dtype=X.dtype, device=X.device)
+    else:
+      _dense('%s: row_sums' % who, row_sums, dt, n, '%d elements' % n)
+    if out is None and row_sums is None:
+      raise ValueError('%s: neither out nor row_sums is wanted' % who)
+    ldo = rows_of('out', out, n, m) if out is not None else m
+    diag_col0 = int(diag_col0)
+    if diag_col0 < -1:
+      raise ValueError('%s: diag_col0 = %d is below -1 (no diagonal)' % (who, diag_col0))
+    if n == 0 or m == 0:
+      if row_sums is not None:
+        row_sums.zero_()
+      return out, row_sums
+    _tile, _kc, use, need = pairwise_plan(dt, n, m, splits)
+    need = need if row_sums is not None else 0
+    ws = self._pairwise_ws.get(X.device)
+    if need and (ws is None or ws.numel() < need):  # (one per device, grown to the largest split seen)
+      ws = self._pairwise_ws[X.device] = torch.empty((need,), dtype=torch.uint8, device=X.device)
+    self._call('spx_pairwise', spx_dtype(dt), PAIR_METRICS[metric], n, m, d, _ptr(X), ldx, _ptr(Y), ldy, gamma,
+               _ptr(out), ldo, _ptr(row_sums), _ptr(row_scale), _ptr(col_scale), diag_col0, float(diag_value), use,
+               _ptr(ws if need else None), ws.numel() if need else 0)
+    return out, row_sums
 
   # --------------------------------------------------------------- sparse
   @staticmethod

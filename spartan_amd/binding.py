@@ -141,6 +141,8 @@ def _signatures():
       'spx_fuzzy_step': ([I, I64, I64, I64, VP, I64, VP, F64, F64, F64, VP, VP, I64, VP, VP, I, VP, SZ, VP], I),
       'spx_nbody_plan': ([I, I64, I64, _I64P, _I64P, ctypes.POINTER(SZ)], I),
       'spx_nbody_accel': ([I, I64, VP, VP, VP, I64, VP, VP, VP, VP, F64, F64, VP, VP, VP, I64, VP, SZ, VP], I),
+      'spx_pairwise_plan': ([I, I64, I64, _I64P, _I64P, _I64P, ctypes.POINTER(SZ)], I),
+      'spx_pairwise': ([I, I, I64, I64, I64, VP, I64, VP, I64, F64, VP, I64, VP, VP, VP, I64, F64, I64, VP, SZ, VP], I),
       'spx_comm_load': ([CP], I),
       'spx_comm_unique_id': ([VP, I64], I),
       'spx_comm_init': ([VP, I64, I, I, VPP], I),
@@ -448,6 +450,30 @@ def nbody_plan(dtype, n_tgt, n_src, splits=0):
   _check(load_library().spx_nbody_plan(spx_dtype(dt), n_tgt, n_src, ctypes.byref(tpb), ctypes.byref(s),
                                        ctypes.byref(nbytes)), 'spx_nbody_plan')
   return int(tpb.value), int(s.value), int(nbytes.value)
+
+
+PAIR_METRICS = {'sqeuclidean': 0, 'euclidean': 1, 'manhattan': 2, 'rbf': 3}  # SPX_PAIR_* of include/spx.h
+
+
+def pairwise_plan(dtype, n, m, splits=0):
+  """(tile, k_chunk, splits, workspace bytes) of spx_pairwise for (n, d)
+  against (m, d) points of ``dtype``, from the library: the edge of the square
+  tile of pairs a workgroup computes at a time (it owns ``tile`` rows), the
+  values of k staged at a time, the contiguous column ranges the work is cut
+  into (``splits`` 0: the library's choice; positive: forced) and the bytes of
+  the float64 row-sum partials a call with ``row_sums`` needs (0 for one
+  range)."""
+  dt = np.dtype(dtype)
+  if dt not in _FLOATS:
+    raise TypeError('pairwise_plan: dtype %s has no pairwise kernel (float32 / float64)' % dt)
+  n, m, splits = int(n), int(m), int(splits)
+  if n < 0 or m < 0:
+    raise ValueError('pairwise_plan: negative size (n %d, m %d)' % (n, m))
+  tile, kc, s = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(splits)
+  nbytes = ctypes.c_size_t(0)
+  _check(load_library().spx_pairwise_plan(spx_dtype(dt), n, m, ctypes.byref(tile), ctypes.byref(kc), ctypes.byref(s),
+                                          ctypes.byref(nbytes)), 'spx_pairwise_plan')
+  return int(tile.value), int(kc.value), int(s.value), int(nbytes.value)
 
 
 def __getattr__(name):

@@ -955,6 +955,9 @@ extern "C" int spx_gemm(int dtype, int64_t M, int64_t N, int64_t K, const void* 
 // ======================================== n-body (all-pairs direct summation)
 #include "nbody_kernels.h"
 
+// ============================ pairwise kernels (affinity matrix, row degrees)
+#include "affinity_kernels.h"
+
 // ============================================================ JIT modules
 extern "C" int spx_module_load(const void* image, size_t nbytes, void** module_out) {
   if (!image || nbytes == 0 || !module_out) return set_err(SPX_EINVAL, "spx_module_load: bad args");

@@ -6,6 +6,7 @@ from .builtins import (abs, add, arange, argmax, argmin, astype, bincount, conca
                        count_zero, exp,
                        ln, log, maximum, max, mean, min, minimum, multiply, norm, ones, power, rand, randn,
                        size, sqrt, square, std, sub, sum, zeros)
+from .affinity import normalized_affinity, pairwise_kernel
 from .dot import dot
 from .eigh import eigh, eigvalsh
 from .filter import compress, take
